@@ -2,8 +2,18 @@
 """Headline benchmark: Paillier encrypt+decrypt ops/sec, 2048-bit key, batch = 1 M.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|cfg2|cfg4|cfg5] [--key-bits B] [--batch B]
-                    [--scaling strong|weak] [--no-cpu-baseline] [--no-extras] [--no-reference-bench]
+                    [--scaling strong|weak] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extras] [--no-reference-bench]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line (metric, value, unit, ms_per_step, ...).
+Everything else the line can carry (the parity check against the oracle, per-kernel times and roofline, the other scaling
+arrangement and the gather time, cpu_baseline, api_level, other_ops, small_batch, the table operating points,
+standard_scheme, reference_bench, configs) is measured only with --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed on this rank (rank 0 only): DIR/
+ciphertexts.npy and DIR/plaintexts.npy, the 32-bit limbs (least significant first) of the encryptions and of their
+decryptions as float64 (exact), one row per element, for a fixed seeded sample of the batch that keeps both files under
+48 MiB together (the whole batch when it fits).  The inputs are seeded, so equal arguments give equal files.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches the N ranks itself (one process per GPU under
 torch.distributed.run, rendezvous on 127.0.0.1) and fails loudly when fewer than N GPUs are visible.
@@ -24,7 +34,7 @@ tests/golden/fixture_keys.json) with a fixed DJN base — built here from plain 
 plaintexts = fixed-point encodings of default_rng(1002).uniform(-1000, 1000, B); randomness r = seeded device
 generator (1024 random bits per element), all uploaded before the timed region.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     — the dominant kernel (k_dec_a: the two CRT half-size modexps) against the measured v_mad_u64_u32
                  peak of the chip (profiles/r01/ubench_valu_mi355x.jsonl); the path is integer-VALU bound, so the
                  "bound" is "valu_int".  frac = EXECUTED multiply-accumulates / peak (kernel quality, <= 1);
@@ -42,7 +52,7 @@ The JSON line also carries
                  Add_CTCT, Add_CTPT, Mul_CTPT at 16 / 64 with its inputs and key) through the PUBLIC API, microseconds per
                  call, with the same composition on the CPU port beside it and a bit-for-bit parity check of every
                  deterministic row (2048-bit configurations only).
-  configs      — default single-GPU invocation only: BASELINE configs[1] (2048-bit, 65 536), configs[3] (3072-bit, 2^20) and
+  configs      — single-GPU headline invocation only: BASELINE configs[1] (2048-bit, 65 536), configs[3] (3072-bit, 2^20) and
                  configs[4] (4096-bit, 2^18) timed in the same run after the headline leg (--config-steps timed steps each),
                  each with value, ms_per_step, the full-batch parity check, per-kernel times, roofline and a CPU sample.
 --config selects the BASELINE.json configuration: headline (2048-bit, 2^20: the metric), cfg2 (2048-bit, 65 536),
@@ -79,6 +89,9 @@ HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md
 # canonical MAC32 per op (CIOS 2L^2+L, 5-bit window): encrypt DJN, decrypt CRT, ct+ct, ct x pt (53-bit e)
 CANON = {1024: (5.35e6, 2.70e6, 16.5e3, 0.79e6), 2048: (41.52e6, 20.86e6, 65.8e3, 3.16e6),
          3072: (138.76e6, 69.61e6, 147.8e3, 7.10e6), 4096: (327.15e6, 163.99e6, 262.7e3, 12.61e6)}
+# --dump-outputs: at most this many bytes of float64 limbs in all, rows drawn with this seed when the batch is larger
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 20260
 BASELINE_METRIC = json.loads((ROOT / "BASELINE.json").read_text())["metric"] if (ROOT / "BASELINE.json").exists() else \
     "Paillier encrypt+decrypt ops/sec, 2048-bit key, batch=1M; 1/2/4/8 MI355X"
 # BASELINE.json configurations this tool can time (same step, same parity check, same roofline / cpu_baseline objects):
@@ -332,6 +345,11 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=None, help="elements in total (strong) or per GPU (weak) per step "
                                                             "(default: the configuration's batch)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
+    ap.add_argument("--full", action="store_true", help="also check and measure everything beyond the headline figure "
+                                                         "(parity, kernel times, roofline, other arrangement, CPU baseline, "
+                                                         "extras, configs); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample) as DIR/<name>.npy in float64")
     ap.add_argument("--no-other-scaling", action="store_true", help="N > 1: skip the second (weak resp. strong) arrangement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip api_level / other_ops / small_batch (profiling runs)")
@@ -410,7 +428,7 @@ def main() -> None:
     def run_leg(scaling: str, ctx: Optional[SimpleNamespace] = None, batch: Optional[int] = None, steps: Optional[int] = None,
                 warmup: Optional[int] = None):
         """Inputs of this rank for one arrangement, W warm-up steps, K timed steps (barrier + synchronize on both sides,
-        maximum over ranks), then the parity check of what was timed."""
+        maximum over ranks), then (--full) the parity check of what was timed."""
         ctx = ctx or ctx0
         key, pub, priv, okey = ctx.key, ctx.pub, ctx.priv, ctx.okey
         batch = args.batch if batch is None else batch
@@ -454,22 +472,23 @@ def main() -> None:
             elapsed = float(t.item())
 
         # ---- correctness of what was just timed (outside the timed region) ---------------------------
-        ok = bool(torch.equal(out, m))
-        nchk = min(B, 4096)
-        got_x = fixedpoint.decode_float64_array(engine.to_host_words(out[:nchk]), expo[:nchk], key.n, key.max_int)
-        ok = ok and bool(np.array_equal(got_x, x[:nchk]))
-        if B:
-            idx = sorted({0, min(1, B - 1), B // 2, B - 1})
-            ct_h = engine.to_host_words(ct[idx])
-            r_h = engine.words_to_ints(engine.to_host_words(r[idx]))
-            m_h = engine.words_to_ints(res[idx])
-            ok = ok and engine.words_to_ints(ct_h) == [orc.encrypt(okey, mm, rr) for mm, rr in zip(m_h, r_h)]
-        if world > 1:
-            flag = torch.tensor([1 if ok else 0], device=device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            ok = bool(flag.item())
-        if not ok:
-            raise SystemExit("bench.py: parity check failed (decrypt(encrypt(m)) != m or ciphertext bits differ from the oracle)")
+        if args.full:
+            ok = bool(torch.equal(out, m))
+            nchk = min(B, 4096)
+            got_x = fixedpoint.decode_float64_array(engine.to_host_words(out[:nchk]), expo[:nchk], key.n, key.max_int)
+            ok = ok and bool(np.array_equal(got_x, x[:nchk]))
+            if B:
+                idx = sorted({0, min(1, B - 1), B // 2, B - 1})
+                ct_h = engine.to_host_words(ct[idx])
+                r_h = engine.words_to_ints(engine.to_host_words(r[idx]))
+                m_h = engine.words_to_ints(res[idx])
+                ok = ok and engine.words_to_ints(ct_h) == [orc.encrypt(okey, mm, rr) for mm, rr in zip(m_h, r_h)]
+            if world > 1:
+                flag = torch.tensor([1 if ok else 0], device=device)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                ok = bool(flag.item())
+            if not ok:
+                raise SystemExit("bench.py: parity check failed (decrypt(encrypt(m)) != m or ciphertext bits differ from the oracle)")
         return SimpleNamespace(scaling=scaling, begin=begin, B=B, x=x, res=res, expo=expo, m=m, r=r, ct=ct, out=out,
                                elapsed=elapsed, total_per_step=total_per_step, steps=steps, warmup=warmup)
 
@@ -493,9 +512,19 @@ def main() -> None:
     begin, B, x, res, expo, m, r, ct, out = leg.begin, leg.B, leg.x, leg.res, leg.expo, leg.m, leg.r, leg.ct, leg.out
     elapsed, total_per_step = leg.elapsed, leg.total_per_step
 
+    # ---- what the last timed step computed: a fixed seeded sample of rows, limbs as exact float64 ----
+    if args.dump_outputs and rank == 0:
+        rows = min(B, DUMP_BYTES // (8 * (ct.shape[1] + out.shape[1])))
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=rows, replace=False)) if rows < B else np.arange(B)
+        pick_d = torch.from_numpy(pick).to(device)
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        for name, t_ in (("ciphertexts", ct), ("plaintexts", out)):
+            np.save(dump_dir / f"{name}.npy", engine.to_host_words(t_[pick_d]).astype(np.float64))
+
     # ---- the final gather of the sharded result (strong scaling; RCCL all-gather over xGMI) ------
     gather_ms = None
-    if args.scaling == "strong" and world > 1:
+    if args.full and args.scaling == "strong" and world > 1:
         full = sharding.gather_rows(ct, args.batch)              # warm-up (communicator set-up)
         torch.cuda.synchronize()
         barrier()
@@ -508,22 +537,23 @@ def main() -> None:
         del full
 
     # ---- per-kernel durations with HIP events on the launch stream (every rank; rank 0 reports) ----
-    kern = kernel_times(ctx0, leg, max(1, min(args.steps, 3)))
-    per_rank_kern = [kern]
-    if world > 1:
-        per_rank_kern = [None] * world
-        dist.all_gather_object(per_rank_kern, kern)
+    kern, per_rank_kern = {}, None
+    if args.full:
+        kern = kernel_times(ctx0, leg, max(1, min(args.steps, 3)))
+        if world > 1:
+            per_rank_kern = [None] * world
+            dist.all_gather_object(per_rank_kern, kern)
 
     # ---- N > 1: the other arrangement, timed the same way (same K, same barriers, same parity check) ----
     other_leg = None
-    if world > 1 and not args.no_other_scaling:
+    if args.full and world > 1 and not args.no_other_scaling:
         o = run_leg("weak" if args.scaling == "strong" else "strong")
         other_leg = {"scaling": o.scaling, "value": o.total_per_step * args.steps / o.elapsed, "unit": "ops/s",
                      "ms_per_step": 1e3 * o.elapsed / args.steps, "batch_total": int(o.total_per_step),
                      "batch_this_rank": o.B, "steps": args.steps, "parity_checked": True}
         del o
 
-    single = rank == 0 and world == 1
+    single = args.full and rank == 0 and world == 1
     extras = single and not args.no_extras
 
     # ---- CPU baseline on the host cores (rank 0, N = 1 only) -------------------------------------
@@ -908,8 +938,8 @@ def main() -> None:
                 "key_bits": KEY_BITS, "batch_per_gpu": B if args.scaling == "weak" else None,
                 "batch_total": int(total_per_step), "scheme": "DJN", "parallelism": f"shard{world}",
             },
-            "roofline": roofline_for(ctx0, B, kern),
-            "per_rank_kernel_ms": per_rank_kern if world > 1 else None,
+            "roofline": roofline_for(ctx0, B, kern) if args.full else None,
+            "per_rank_kernel_ms": per_rank_kern,
             "gather_ms": gather_ms,
             "ranks_seen": ranks_seen,
             "collective_backend": (backend if world > 1 else None),
@@ -921,14 +951,15 @@ def main() -> None:
             "small_batch": small,
             "fixed_base_table_points": table_points,
             "reference_bench": ref_bench,
-            "parity_checked": True,
+            "parity_checked": args.full,
         }
         # ---- the LAST keys of the line (the driver keeps the tail of stdout): every configuration's number, compact ----
         rl = line["roofline"]
-        line["roofline"]["note_traffic"] = (
-            None if not rl.get("traffic") else
-            f"traffic / algorithmic bytes = {rl['traffic'] / (BYTES_DEC * B):.0f}x (per-element window tables in HBM scratch) = "
-            f"{rl['traffic'] / max(kern.get('k_dec_a', 0.0) * 1e-3, 1e-9) / 1e9:.0f} GB/s of {HBM_PEAK_GBS:.0f}: not the limiter")
+        if rl:
+            rl["note_traffic"] = (
+                None if not rl.get("traffic") else
+                f"traffic / algorithmic bytes = {rl['traffic'] / (BYTES_DEC * B):.0f}x (per-element window tables in HBM scratch) = "
+                f"{rl['traffic'] / max(kern.get('k_dec_a', 0.0) * 1e-3, 1e-9) / 1e9:.0f} GB/s of {HBM_PEAK_GBS:.0f}: not the limiter")
         line["standard_scheme"] = std_scheme
         if ref_bench:
             line["reference_bench_summary_us"] = {
@@ -937,7 +968,7 @@ def main() -> None:
                 for k_, v_ in ref_bench.get("rows", {}).items()}           # [GPU public API, best CPU-port figure]
         line["configs_summary"] = {
             "fields": ["ops_per_s", "ms_per_step", "roofline_frac_executed", "k_encrypt_ms", "k_dec_a_ms", "cpu_ops_per_s"],
-            "headline": [round(value), round(1e3 * elapsed / args.steps, 2), rl["frac"] and round(rl["frac"], 4),
+            "headline": [round(value), round(1e3 * elapsed / args.steps, 2), rl and rl["frac"] and round(rl["frac"], 4),
                          kern.get("k_encrypt(djn)") and round(kern["k_encrypt(djn)"], 2), kern.get("k_dec_a") and round(kern["k_dec_a"], 2),
                          cpu and round(cpu["value"])],
             **({n_: [round(b_["value"]), round(b_["ms_per_step"], 2), b_["roofline"]["frac"] and round(b_["roofline"]["frac"], 4),

@@ -20,7 +20,7 @@ def test_bench_two_ranks_on_one_gpu(scaling):
     env = dict(os.environ, PAI_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "6000",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "6000", "--full",
            "--no-cpu-baseline", "--no-extras"] + (["--scaling", "weak"] if scaling == "weak" else [])     # strong is the default
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert res.returncode == 0, res.stderr[-3000:]
@@ -50,7 +50,7 @@ def test_bench_eight_ranks_on_one_gpu(config, scaling, batch):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", str(batch),
-           "--config", config, "--scaling", scaling, "--no-cpu-baseline", "--no-extras"]
+           "--config", config, "--scaling", scaling, "--full", "--no-cpu-baseline", "--no-extras"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -73,7 +73,7 @@ def test_bench_single_gpu_config_lines_carry_roofline_and_cpu_baseline():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PAI_BENCH_BACKEND")}
     for config, bits, nl, prof_batch in (("cfg5", 4096, 72, 1 << 18), ("cfg4", 3072, 56, 1 << 20)):
         cmd = [sys.executable, str(ROOT / "bench.py"), "--config", config, "--batch", "4096", "--steps", "1", "--warmup", "1",
-               "--no-extras", "--cpu-seconds", "2"]
+               "--full", "--no-extras", "--cpu-seconds", "2"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
         assert res.returncode == 0, res.stderr[-3000:]
         line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -82,6 +82,41 @@ def test_bench_single_gpu_config_lines_carry_roofline_and_cpu_baseline():
         assert f"k_dec_a_padic<{nl}>" in rf["kernel"] and 0 < rf["frac"] < 1.2 and rf["peak_sustained"] < rf["peak"]
         assert rf["traffic"] is not None and rf["traffic_source"]["profile_batch"] == prof_batch
         assert cpu["value"] > 0 and cpu["cores"] >= 1 and "port" in cpu["kind"]
+
+
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline line alone, --steps timed steps, and --dump-outputs writes the last
+    step's ciphertexts and plaintexts; two runs with the same arguments write the same files, the plaintexts are the
+    encodings of the seeded inputs and the ciphertexts decrypt to them under the oracle."""
+    import numpy as np
+
+    from oracle import paillier_oracle as orc
+    from pailliercryptolib_python_amd import fixedpoint
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PAI_BENCH_BACKEND")}
+    batch, dumps = 4096, []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--batch", str(batch), "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(out_dir)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "ops/s" and line["higher_is_better"] is True
+        assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(batch * 1e3 / line["ms_per_step"])
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["configs"] is None
+        dumps.append({name: np.load(out_dir / f"{name}.npy") for name in ("ciphertexts", "plaintexts")})
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    ct, pt = dumps[0]["ciphertexts"], dumps[0]["plaintexts"]
+    assert ct.dtype == pt.dtype == np.float64 and ct.shape == (batch, 128) and pt.shape == (batch, 64)
+    fx = json.loads((ROOT / "tests" / "golden" / "fixture_keys.json").read_text())["2048"]
+    key = orc.make_key(int(fx["p"], 16), int(fx["q"], 16), djn_x=0x1234567, bits=2048)
+    x = np.random.default_rng(1002).uniform(-1000.0, 1000.0, batch)
+    res_, _ = fixedpoint.encode_float64_array(x, key.n, 64)
+    assert np.array_equal(pt, res_.astype(np.float64))
+    for i in (0, batch // 2, batch - 1):
+        c = int.from_bytes(ct[i].astype("<u4").tobytes(), "little")
+        assert orc.decrypt_crt(key, c) == int.from_bytes(res_[i].astype("<u4").tobytes(), "little")
 
 
 def test_bench_refuses_more_ranks_than_gpus():

@@ -10,6 +10,6 @@ mkdir -p $OUT
 SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer -Xarch_host -g"
 hipcc --offload-arch=gfx950 -O1 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=1048576 $SAN -c $C/paillier_capi.hip -o $OUT/paillier_capi_asan.o
 OTHERS=$(ls $C/build/*.o | grep -v paillier_capi.o)
-hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan -o $OUT/lib_asan.so $OTHERS $OUT/paillier_capi_asan.o
+hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan -o $OUT/lib_asan.so $OTHERS $OUT/paillier_capi_asan.o
 rm -f $OUT/paillier_capi_asan.o
 echo $OUT/lib_asan.so

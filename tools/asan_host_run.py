@@ -30,11 +30,15 @@ for n in (0, 1, 7, 1000, (1 << 20) + 3):
 h = C.c_void_p()
 nn = np.array([0xFFFFFFFB, 0xFFFFFFFF, 0xFFFFFFFF, 0x7FFFFFFF], dtype=np.uint32)
 rc = lib.pai_pubkey_create(nn.ctypes.data_as(C.c_void_p), 4, 128, None, 0, 0, 0, C.byref(h))
-assert rc == _native.PAI_E_NODEVICE or rc == 0
+assert rc == _native.PAI_E_NODEVICE
 print("asan host run: ok")
 '''
-env = dict(os.environ, PAI_NATIVE_LIB=lib, LD_PRELOAD=rt[-1], ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-           PYTHONPATH=ROOT)
+# the sanitizer runtime must come first in the preload list; whatever the environment already preloads stays after it
+preload = ":".join([rt[-1]] + [p for p in os.environ.get("LD_PRELOAD", "").split(":") if p])
+# host code only: the child sees no GPU (the HIP runtime would otherwise hand its device-memory allocations to the
+# sanitizer's device allocator), so pai_pubkey_create takes the no-device path on every machine
+env = dict(os.environ, PAI_NATIVE_LIB=lib, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+           PYTHONPATH=ROOT, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
 res = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True, cwd=ROOT)
 sys.stdout.write(res.stdout[-2000:]); sys.stderr.write(res.stderr[-6000:])
 bad = res.returncode != 0 or "ERROR: AddressSanitizer" in res.stderr or "runtime error:" in res.stderr

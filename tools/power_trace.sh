@@ -4,7 +4,7 @@
 OUT=$PWD/gpurun_out/power_trace.txt
 mkdir -p $(dirname $OUT)
 rocm-smi --showmaxpower --showpower --showclocks 2>/dev/null | grep -iE "sclk|power|Max" > $OUT
-( python bench.py --no-cpu-baseline --steps 6 --warmup 1 > gpurun_out/power_bench.json 2>/dev/null ) &
+( python bench.py --full --no-cpu-baseline --steps 6 --warmup 1 > $(dirname $OUT)/power_bench.json 2>/dev/null ) &
 BP=$!
 sleep 6
 for i in $(seq 1 40); do
@@ -14,5 +14,5 @@ for i in $(seq 1 40); do
   sleep 0.25
 done
 wait $BP
-tail -c 300 gpurun_out/power_bench.json | cut -c1-200
+tail -c 300 $(dirname $OUT)/power_bench.json | cut -c1-200
 grep -iE "sclk|Average Graphics|Current Socket" $OUT | sort | uniq -c | sort -rn | head -20

@@ -6,8 +6,8 @@ TAG=${1:-final}
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="python $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-configs"
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+B="python $PWD/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras --no-configs"
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- $B > $OUT/bench_under_rocprofv3.json 2> $OUT/trace.err)
 DB=$(find $OUT/trace -name "*.db" | head -1)
 [ -n "$DB" ] && python tools/rocpd_summary.py $DB > $OUT/kernel_stats.csv
