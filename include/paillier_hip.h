@@ -245,6 +245,20 @@ int pai_ct_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t count, size_t
 int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_ct_inv, size_t R, size_t K, size_t M,
                     const uint32_t* d_e, int e_words, int ebits_max, const uint8_t* d_sign, uint32_t* d_out, void* stream);
 
+/* Segment products behind PaillierEncryptedNumber.segment_sum (extension; no reference counterpart): S Horner chains over
+ * gathered rows,  d_out[s] = the chain  acc <- acc^(2^d_shift[j]) * d_ct[d_rows[j]]  over members j = d_offsets[s] ..
+ * d_offsets[s+1] - 1, in the wire form (canonical residues), the shift of a chain's first member ignored; an empty chain gives 1.
+ * With the members of a segment sorted by exponent and shift = the step to the previous member's exponent, this is
+ * prod_j ct_j^(2^(E_s - e_j)) mod n^2 — the exponent-aligned sum of the segment — at one Montgomery product per member plus
+ * one per unit of the segment's exponent spread.  d_ct: [N][ct_words] at domain tag `tag` (pai_ct_mont_mul; 0 = wire form,
+ * |tag| <= 46); d_rows: uint32 row indices (NULL: member j is row j); d_shift: int32 steps >= 0 (NULL: all 0); d_offsets: int64
+ * [S + 1], nondecreasing, d_offsets[S] = the number of members.  A row >= N is skipped and a negative shift counts as 0; either
+ * sets bit 2 of the handle's status word (pai_pubkey_status) and never reads outside d_ct.  Long segments are cut into chunks
+ * whose partial products are combined by further levels on the handle's scratch (PAI_TUNE segprod_chunk: the chunk length).
+ * Reads d_offsets[S] and the longest segment back first (one synchronisation of `stream`); the rest is asynchronous. */
+int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, const uint32_t* d_rows, const int32_t* d_shift,
+                        const int64_t* d_offsets, size_t S, uint32_t* d_out, void* stream);
+
 /* Exponent alignment, ipcl_python.py:570-741 (ct * 2^delta as ciphertext^(2^delta)):
  * for delta_i > 0: d_ct[i] <- d_ct[i]^(2^delta_i) mod n^2; other elements are left untouched.
  * Batches of >= 16384 elements (PAI_POW2_DIGIT_MIN) on keys up to 2048 bits read the largest shift back first (this
@@ -259,8 +273,9 @@ int pai_ct_pow2_hint(const pai_pubkey* pk, uint32_t* d_ct, const int32_t* d_delt
  * clear != 0): bit 0 — pai_ct_invert_async met a ciphertext that is not invertible modulo n^2 (its output rows are then
  * undefined); bit 1 — a pai_ct_pow2_hint call was given a max_delta below a shift of its batch on the digit-engine path
  * (batches >= PAI_POW2_DIGIT_MIN on keys up to 2048 bits, hints the digit path serves; the raised ciphertexts of that call are
- * then wrong — a hint outside that range runs the lane-group kernel, which is correct for any shift, and flags nothing).  The
- * Python layer computes its hints from host arrays and uses pai_ct_invert_flag, so it never depends on this word. */
+ * then wrong — a hint outside that range runs the lane-group kernel, which is correct for any shift, and flags nothing); bit 2 —
+ * a pai_ct_segment_prod call met a member row >= N (skipped) or a negative shift (taken as 0).  The Python layer computes its
+ * hints from host arrays, uses pai_ct_invert_flag and builds its segment plans itself, so it never depends on this word. */
 int pai_pubkey_status(const pai_pubkey* pk, int* status_out, int clear, void* stream);
 
 

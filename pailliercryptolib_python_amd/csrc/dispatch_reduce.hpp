@@ -58,6 +58,107 @@ int pai_ct_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t count, size_t
     });
 }
 
+// Segment products behind PaillierEncryptedNumber.segment_sum (extension).  Segments are badly unbalanced in practice (one bin
+// often holds most rows), so no chain runs over a whole segment: every level cuts each segment's member list into chunks of at
+// most C members (k_seg_chunk_scan / k_seg_chunk_expand), runs one chain per chunk into a partial row (k_segprod) and hands the
+// partials on as the next level's members — row k = chunk k, tag 0 (wire form), shift = the sum of the chunk's member shifts
+// (the partial carries the exponent of its last member; the first chunk's shift is ignored like any first member's).  The
+// last level runs one chain per segment into d_out.  C of the first level fills the device with chains; later levels hold a
+// few partials per segment and take short chunks (latency: one product per member and level).
+int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, const uint32_t* d_rows, const int32_t* d_shift,
+                        const int64_t* d_offsets, size_t S, uint32_t* d_out, void* stream) {
+    return guarded([&] {
+        require(pk && d_offsets && d_out, "NULL argument");
+        require(std::abs(tag) <= RPOW_SPAN - 2, "pai_ct_segment_prod: domain tag out of range");
+        require(N < ((size_t)1 << 31) && S < ((size_t)1 << 30), "pai_ct_segment_prod: too many rows or segments for one call");
+        if (S == 0) return;
+        std::lock_guard<std::mutex> lk(pk->mu);
+        DeviceScope scope_(pk->device);
+        hipStream_t s = (hipStream_t)stream;
+        const uint32_t* rpow = rpow_table(pk);
+        const GeoOps* g = pk->msq.geo;
+        const size_t W = (size_t)pk->ct_words;
+        // the member count and the longest segment (one read-back: the sizes of the levels).  seg_plan is the handle's scratch that
+        // an earlier call on another stream may still read: ordered like every other user (OrderScope), closed before the sync
+        int64_t stats[2] = {0, 0};
+        {
+            OrderScope order_0(pk->order, s);
+            pk->seg_plan.ensure(2 * sizeof(int64_t));
+            hipLaunchKernelGGL(k_seg_stats, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, d_offsets, (int)S, pk->seg_plan.as<int64_t>());
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(stats, pk->seg_plan.p, sizeof(stats), hipMemcpyDeviceToHost, s));
+            order_0.done();
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+        const size_t M = stats[0] > 0 ? (size_t)stats[0] : 0;
+        size_t lmax = stats[1] > 0 ? (size_t)stats[1] : 0;
+        require(M == 0 || d_ct != nullptr, "NULL argument");
+        const size_t C = segprod_chunk((size_t)pk->dev.ncu, g->epb, M);   // first-level chunk (path_ranges.hpp)
+        // level sizes: a level of m members in S segments has at most m / C + S chunks
+        size_t levels = 0, rows_max = 0;
+        {
+            size_t m = M, l = lmax, c = C;
+            while (l > c) {
+                m = std::min(m, m / c + S);
+                rows_max = std::max(rows_max, m);
+                l = (l + c - 1) / c;
+                c = std::min<size_t>(C, 4) < 2 ? 2 : std::min<size_t>(C, 4);
+                ++levels;
+            }
+        }
+        uint32_t* part[2] = {nullptr, nullptr};
+        int32_t* ssum[2] = {nullptr, nullptr};
+        int64_t *cstart[2] = {nullptr, nullptr}, *coff = nullptr;
+        OrderScope order_(pk->order, s);
+        if (levels) {
+            const size_t rb = rows_max * W * 4;
+            pk->seg_partial.ensure(2 * rb);
+            part[0] = pk->seg_partial.as<uint32_t>();
+            part[1] = part[0] + rows_max * W;
+            const size_t n64 = 2 * (S + 1) + (rows_max + 1), n32 = 2 * rows_max;
+            pk->seg_plan.ensure(n64 * 8 + n32 * 4);
+            cstart[0] = pk->seg_plan.as<int64_t>();
+            cstart[1] = cstart[0] + (S + 1);
+            coff = cstart[1] + (S + 1);
+            ssum[0] = reinterpret_cast<int32_t*>(coff + rows_max + 1);
+            ssum[1] = ssum[0] + rows_max;
+        }
+        int* status = status_word(pk, s);
+        g_last_times.clear();
+        auto chains = [&](const uint32_t* ct, size_t n, int tg, const uint32_t* rows, const int32_t* sh, const int64_t* off, size_t count,
+                          uint32_t* out, int32_t* shift_sum) {
+            SegArgs A;
+            A.ct = ct; A.rows = rows; A.shift = sh; A.offsets = off; A.out = out; A.shift_sum = shift_sum; A.status = status;
+            A.n = (int)n; A.tag = tg; A.chains = (int)count;
+            ScopedKernelTimer t("k_segprod", s);
+            g->segprod(s, grid_for(g, count, pk->dev.ncu), pk->msq.d_ctx, A, pk->ct_words, rpow);
+            t.stop();
+            HIP_CHECK(hipGetLastError());
+        };
+        const uint32_t* ct = d_ct;
+        const uint32_t* rows = d_rows;
+        const int32_t* sh = d_shift;
+        const int64_t* off = d_offsets;
+        size_t n = N, m = M, c = C;
+        int tg = tag;
+        for (size_t lev = 0; lev < levels; ++lev) {
+            const int b = (int)(lev & 1);
+            const size_t mn = std::min(m, m / c + S);              // chains of this level (the chunks; the tail of them empty)
+            hipLaunchKernelGGL(k_seg_chunk_scan, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, off, (int)S, (int64_t)c, cstart[b]);
+            HIP_CHECK(hipGetLastError());
+            const int eg = (int)std::min<size_t>((mn + 1 + 255) / 256, 1024);
+            hipLaunchKernelGGL(k_seg_chunk_expand, dim3(eg), dim3(256), 0, s, off, cstart[b], (int)S, (int64_t)c, coff, mn);
+            HIP_CHECK(hipGetLastError());
+            chains(ct, n, tg, rows, sh, coff, mn, part[b], ssum[b]);
+            ct = part[b]; n = mn; tg = 0; rows = nullptr; sh = ssum[b]; off = cstart[b];
+            m = mn;
+            c = std::min<size_t>(C, 4) < 2 ? 2 : std::min<size_t>(C, 4);
+        }
+        chains(ct, n, tg, rows, sh, off, S, d_out, nullptr);
+        order_.done();
+    });
+}
+
 // Multi-exponentiation behind the matrix products (kernels_padic_enc.hpp: k_mexp_table_padic, k_mexp_padic)
 int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_ct_inv, size_t R, size_t K, size_t M,
                     const uint32_t* d_e, int e_words, int ebits_max, const uint8_t* d_sign, uint32_t* d_out, void* stream) {

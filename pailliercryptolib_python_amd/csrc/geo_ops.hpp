@@ -55,6 +55,8 @@ struct GeoOps {
                  uint32_t* out, int nlanes);
     // out = a * b mod M on wire-form rows by one most-significant-limb-first product (k_modmul_msb; NULL on the latency geometries)
     void (*modmul_msb)(hipStream_t, int grid, const MsbCtx*, const uint32_t* a, const uint32_t* b, uint32_t* out, int n, int w32);
+    // segment products (k_segprod): one Horner chain of gathered rows per output; rpow as for addn
+    void (*segprod)(hipStream_t, int grid, const MontCtx*, SegArgs, int w32, const uint32_t* rpow);
 };
 
 const GeoOps* geo_ops_36x1();

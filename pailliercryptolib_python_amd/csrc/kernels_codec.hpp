@@ -231,4 +231,78 @@ k_pow2_expo(const int32_t* __restrict__ delta, int bcast, size_t n, uint32_t* __
     }
 }
 
+// ---- chunk plans of pai_ct_segment_prod (segments off[s] .. off[s+1] of a member list, cut into chunks of <= C members) ----
+// One workgroup of 256 threads over the S segments: thread t owns a contiguous range of them.
+constexpr int SEG_PLAN_THREADS = 256;
+
+// stats[0] = off[S] (the member count), stats[1] = the longest segment
+__global__ void __launch_bounds__(SEG_PLAN_THREADS)
+k_seg_stats(const int64_t* __restrict__ off, int S, int64_t* __restrict__ stats) {
+    __shared__ int64_t red[SEG_PLAN_THREADS];
+    const int t = threadIdx.x, per = (S + SEG_PLAN_THREADS - 1) / SEG_PLAN_THREADS;
+    int64_t mx = 0;
+    for (int s = t * per; s < min(S, (t + 1) * per); ++s) {
+        const int64_t len = off[s + 1] - off[s];
+        mx = len > mx ? len : mx;
+    }
+    red[t] = mx;
+    __syncthreads();
+    for (int h = SEG_PLAN_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) red[t] = red[t + h] > red[t] ? red[t + h] : red[t];
+        __syncthreads();
+    }
+    if (t == 0) {
+        stats[0] = off[S];
+        stats[1] = red[0];
+    }
+}
+
+// cstart[s] = chunks of the segments before s (exclusive prefix of ceil(len / C)), cstart[S] = all chunks
+__global__ void __launch_bounds__(SEG_PLAN_THREADS)
+k_seg_chunk_scan(const int64_t* __restrict__ off, int S, int64_t C, int64_t* __restrict__ cstart) {
+    __shared__ int64_t sum[SEG_PLAN_THREADS];
+    const int t = threadIdx.x, per = (S + SEG_PLAN_THREADS - 1) / SEG_PLAN_THREADS;
+    const int s0 = min(S, t * per), s1 = min(S, (t + 1) * per);
+    int64_t own = 0;
+    for (int s = s0; s < s1; ++s) {
+        const int64_t len = off[s + 1] - off[s];
+        own += len > 0 ? (len + C - 1) / C : 0;
+    }
+    sum[t] = own;
+    __syncthreads();
+    for (int d = 1; d < SEG_PLAN_THREADS; d <<= 1) {               // inclusive scan (Hillis-Steele)
+        const int64_t v = t >= d ? sum[t - d] : 0;
+        __syncthreads();
+        sum[t] += v;
+        __syncthreads();
+    }
+    int64_t run = sum[t] - own;
+    for (int s = s0; s < s1; ++s) {
+        cstart[s] = run;
+        const int64_t len = off[s + 1] - off[s];
+        run += len > 0 ? (len + C - 1) / C : 0;
+    }
+    if (t == SEG_PLAN_THREADS - 1) cstart[S] = sum[t];
+}
+
+// coff[k] (k <= U) = the first member of chunk k; chunks k >= cstart[S] are empty (coff = off[S])
+__global__ void __launch_bounds__(256)
+k_seg_chunk_expand(const int64_t* __restrict__ off, const int64_t* __restrict__ cstart, int S, int64_t C,
+                   int64_t* __restrict__ coff, size_t U) {
+    const int64_t total = cstart[S], M = off[S];
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k <= U; k += (size_t)gridDim.x * blockDim.x) {
+        if ((int64_t)k >= total) {
+            coff[k] = M;
+            continue;
+        }
+        int lo = 0, hi = S;                                         // the last s with cstart[s] <= k
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (cstart[mid] <= (int64_t)k) lo = mid;
+            else hi = mid;
+        }
+        coff[k] = off[lo] + ((int64_t)k - cstart[lo]) * C;
+    }
+}
+
 }  // namespace pai

@@ -1109,4 +1109,188 @@ k_addn(const MontCtx* __restrict__ ctx, AddnArgs A, uint32_t* out, int n, int w3
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Segment products (PaillierEncryptedNumber.segment_sum, extension): one Horner chain per lane group,
+//     out[s] = the chain acc <- acc^(2^shift_j) * ct[rows_j] over members j = offsets[s] .. offsets[s+1]-1,
+// the shift of the chain's first member ignored (it would square the empty product 1).  With the members of a segment sorted
+// by exponent, shift_j = e_j - e_{j-1} and the chain is prod_j ct_j^(2^(E - e_j)), E the last member's exponent.
+//
+// Every lane group walks its own chain: per step it picks ONE product — the next member (acc * ct_row, gathered by row index),
+// a squaring (acc * acc), or a move of the accumulator's power of R (acc * R^m from the key's table) — and the wave runs
+// one rolled loop until its longest chain is done, so a chain pays for its own members and exponent steps, not for its
+// neighbours'.  Montgomery bookkeeping as in k_addn: acc holds (product) R^c, c per lane; a member at R^tag turns c into
+// c + tag - 1; before the squarings of a shift c is brought to 1 (acc * R^(2-c): squarings keep c = 1); a run of equal
+// exponents is brought to c = 1 whenever the next member would take c out of |2 - c|, |1 - c| <= RPOW_SPAN; the last step
+// is acc * R^(1-c) (skipped when c = 0), and cond_sub gives the canonical residue.  Empty chains give 1.
+// Rows >= n are skipped and a negative shift counts as 0; both set bit 2 of *status (the handle's sticky word).
+struct SegArgs {
+    const uint32_t* ct;              // [n][w32] rows at R^tag
+    const uint32_t* rows;            // [members] source rows, or NULL: member j is row j
+    const int32_t* shift;            // [members] exponent steps, or NULL: all 0
+    const int64_t* offsets;          // [chains + 1]
+    uint32_t* out;                   // [chains][w32], wire form
+    int32_t* shift_sum;              // NULL, or [chains]: the sum of each chain's member shifts (the next pass's shift)
+    int* status;
+    int n, tag, chains;
+};
+
+// Copies the packed rows `row` (per lane, the lane group's; < 0: none) of this wave's lane groups into their staging rows
+// (load_tile for rows that are not consecutive).  Rows without a source keep whatever the stage held.
+template <class G>
+PAI_DEV void gather_tile(uint32_t* stage, const uint32_t* __restrict__ src, int row, int W32) {
+    using WT = WaveTile<G>;
+    uint32_t* dst = WT::slice(stage);
+    const int lane = WT::lane();
+    wave_lds_fence();
+    if ((W32 & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+        const int wv = W32 >> 2;
+        const int total = WT::EPW * wv;
+        const uint32_t inv = (65536u + (uint32_t)wv - 1u) / (uint32_t)wv;     // c / wv == (c * inv) >> 16 for c < 1024
+        const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        uint4 v[WT::IT4];
+        int re[WT::IT4];
+#pragma unroll
+        for (int it = 0; it < WT::IT4; ++it) {
+            const int c = lane + it * 64;
+            const int cc = c < total ? c : total - 1;
+            const int e = (int)(((uint32_t)cc * inv) >> 16), k = cc - e * wv;
+            const int r = __shfl(row, e * G::T, 64);
+            re[it] = c < total ? r : -1;
+            v[it] = make_uint4(0u, 0u, 0u, 0u);
+            if (re[it] >= 0) v[it] = s4[(size_t)r * wv + k];
+        }
+#pragma unroll
+        for (int it = 0; it < WT::IT4; ++it) {
+            const int c = lane + it * 64;
+            const int e = (int)(((uint32_t)c * inv) >> 16), k = c - e * wv;
+            if (re[it] >= 0) d4[e * WT::SV + k] = v[it];
+        }
+    } else {                                                 // odd word counts / unaligned rows (wave-uniform trip count: the shuffle)
+        constexpr int TOT = WT::EPW * G::SW;
+        for (int b = 0; b < TOT; b += 64) {
+            const int i = b + lane, ic = i < TOT ? i : TOT - 1;
+            const int e = ic / G::SW, k = ic - e * G::SW;
+            const int r = __shfl(row, e * G::T, 64);
+            if (i < TOT && k < W32 && r >= 0) dst[i] = src[(size_t)r * W32 + k];
+        }
+    }
+    wave_lds_fence();
+}
+
+template <class G>
+__global__ void __launch_bounds__(BLOCK_THREADS, 2)
+k_segprod(const MontCtx* __restrict__ ctx, SegArgs A, int w32, const uint32_t* __restrict__ rpow) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    using WT = WaveTile<G>;
+    uint32_t* stage = lds + G::LDS_WORDS + G::NL;
+    typename G::NM nm;
+    load_modulus<G>(nm, ctx, lds);
+    const uint32_t n0inv = ctx->n0inv;
+    constexpr int WPB = BLOCK_THREADS / 64;
+    enum { OP_NONE = 0, OP_FIRST, OP_MEMBER, OP_SQUARE, OP_RPOW };
+    const int wtiles = (A.chains + WT::EPW - 1) / WT::EPW;
+    clear_stage<G>(stage);
+    const uint32_t* o_lds = lds + G::elem();             // column of this element in the [limb][element] operand buffer
+    const int per_wave = (wtiles + (int)gridDim.x * WPB - 1) / ((int)gridDim.x * WPB);
+    const int wt_begin = ((int)blockIdx.x * WPB + WT::wave()) * per_wave;
+    const int wt_end = min(wtiles, wt_begin + per_wave);
+    for (int wt = wt_begin; wt < wt_end; ++wt) {
+        const int row0 = wt * WT::EPW;
+        const int ch = row0 + WT::lane() / G::T;         // this lane group's chain
+        long long j = 0, jend = 0;
+        if (ch < A.chains) {
+            j = A.offsets[ch];
+            jend = A.offsets[ch + 1];
+            jend = jend > j ? jend : j;
+        }
+        uint32_t acc[G::NLL];
+        set_plain_one<G>(acc);                           // the empty product
+        int c = 0;                                       // acc holds (product so far) R^c
+        int sq = 0;                                      // squarings still owed before member j joins
+        int src = -1;                                    // member j's row once read (-1: not read yet)
+        int ssum = 0;
+        bool has = false, done = false, bad = false;
+        while (__any(!done)) {                           // wave-uniform: one product per iteration at most
+            int op = OP_NONE, m = 0;
+            if (!done) {
+                if (j < jend) {
+                    if (src < 0) {
+                        const uint32_t r = A.rows ? A.rows[j] : (uint32_t)j;
+                        const int s = A.shift ? A.shift[j] : 0;
+                        ssum += s;
+                        bad |= s < 0 || r >= (uint32_t)A.n;
+                        sq = has && s > 0 ? s : 0;
+                        src = r < (uint32_t)A.n ? (int)r : -1;
+                        if (src < 0) ++j;                // a bad row is skipped
+                    }
+                    if (src >= 0) {
+                        const int cn = c + A.tag - 1;    // c after the member
+                        if (!has) op = OP_FIRST;
+                        else if (sq > 0 && c == 1) op = OP_SQUARE;
+                        else if (sq > 0 || 2 - cn > RPOW_SPAN || cn - 1 > RPOW_SPAN) { op = OP_RPOW; m = 2 - c; }
+                        else op = OP_MEMBER;
+                    }
+                } else if (has && c != 0) {
+                    op = OP_RPOW;                        // the way out: * R^(1 - c)
+                    m = 1 - c;
+                } else {
+                    done = true;
+                }
+            }
+            const bool fetch = op == OP_FIRST || op == OP_MEMBER;
+            uint32_t y[G::NLL];
+#pragma unroll
+            for (int i = 0; i < G::NLL; ++i) y[i] = acc[i];              // the squaring's right operand
+            if (__any(fetch)) {
+                __builtin_amdgcn_s_setprio(2);
+                gather_tile<G>(stage, A.ct, fetch ? src : -1, w32);
+                uint32_t t[G::NLL];
+                unpack_row<G>(t, stage);
+                __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) y[i] = fetch ? t[i] : y[i];
+            }
+            if (__any(op == OP_RPOW)) {
+                const int mc = m < -RPOW_SPAN ? -RPOW_SPAN : (m > RPOW_SPAN ? RPOW_SPAN : m);
+                const uint32_t* p = rpow + (size_t)(RPOW_SPAN + mc) * G::NL + G::NLL * G::gl();
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) {
+                    const uint32_t v = p[i];
+                    y[i] = op == OP_RPOW ? v : y[i];
+                }
+            }
+            const bool mul = op == OP_MEMBER || op == OP_SQUARE || op == OP_RPOW;
+            if (__any(mul)) {
+                stage_b<G>(y, lds);
+                uint32_t r[G::NLL];
+                mont_mul<G::NLL, G::U, G::T>(r, acc, o_lds, G::EPB, nm, n0inv);
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) acc[i] = mul ? r[i] : (op == OP_FIRST ? y[i] : acc[i]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) acc[i] = op == OP_FIRST ? y[i] : acc[i];
+            }
+            if (op == OP_FIRST) { has = true; c = A.tag; }
+            if (op == OP_MEMBER) c += A.tag - 1;
+            if (op == OP_FIRST || op == OP_MEMBER) { ++j; src = -1; }
+            if (op == OP_SQUARE) --sq;
+            if (op == OP_RPOW) {                          // R^(2-c) before a member: c = 1; R^(1-c) after the last: wire form
+                done = j >= jend;
+                c = done ? 0 : 1;
+            }
+        }
+        cond_sub<G::NLL, G::T>(acc, nm);
+        __builtin_amdgcn_s_setprio(2);
+        pack_row<G>(acc, stage);
+        const int rows = min(WT::EPW, A.chains - row0);
+        store_tile<G>(stage, A.out + (size_t)row0 * w32, rows, w32);
+        __builtin_amdgcn_s_setprio(0);
+        if (G::gl() == 0 && ch < A.chains) {
+            if (A.shift_sum) A.shift_sum[ch] = ssum;
+            if (bad && A.status) atomicOr(A.status, 4);
+        }
+    }
+}
+
 }  // namespace pai

@@ -162,6 +162,17 @@ static int lat_add_wire_scale(int key_bits) {
     return key_bits <= 1024 ? 6 : key_bits <= 2048 ? 5 : key_bits <= 3072 ? 2 : key_bits <= 4096 ? 4 : 2;
 }
 
+// ---- segment products ---------------------------------------------------------------------------------------------------------
+// PAI_TUNE segprod_chunk: members per chain of the first level of pai_ct_segment_prod (>= 1; tests force 1 / 2 / 3 and with them
+// several levels).  Default: one round of resident chains (two workgroups of epb lane groups per CU) over all members, at least 4.
+// Measured at 2048-bit keys, 2^20 rows x 8 features (tools/segsum_time.py): 31.3 ms for 2^23 members, 0.59 x the in-chain product rate.
+static size_t segprod_chunk(size_t ncu, int epb, size_t members) {
+    long long v;
+    if (knob_tune("segprod_chunk", &v) && v >= 1) return (size_t)v;
+    const size_t want = std::max<size_t>(1, ncu * (size_t)epb * 2);
+    return std::max<size_t>(4, (members + want - 1) / want);
+}
+
 // ---- the switch points of one key, for tests and probes (pai_path_edges) --------------------------------------------------------
 // every batch size E at which the path of `op` (0 decrypt, 1 DJN encrypt, 2 ct x pt, 3 ct + ct) may change between N = E and
 // N = E + 1 on a device of ncu compute units (a superset: a path a key cannot take leaves its edge in the list)

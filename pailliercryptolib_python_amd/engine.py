@@ -385,6 +385,24 @@ class PublicKeyHandle:
         _native.check(self.lib.pai_ct_prod(self.h, _ptr(ct), ct.shape[0], int(groups), _ptr(out), _stream(self.device)))
         return out
 
+    def ct_segment_prod(self, ct: torch.Tensor, rows: Optional[torch.Tensor], shift: Optional[torch.Tensor], offsets: torch.Tensor,
+                        tag: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """S = len(offsets) - 1 Horner chains acc <- acc^(2^shift[j]) * ct[rows[j]] over members offsets[s] .. offsets[s+1]-1, wire
+        form out (pai_ct_segment_prod; empty chains give 1).  ct: rows at domain tag `tag`; rows: uint32 as int32 [M] (None: row j);
+        shift: int32 [M] (None: all 0); offsets: int64 [S + 1].  Synchronises the current stream once (the plan's sizes)."""
+        self._chk(ct, self.ct_words, "ct")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or not offsets.is_contiguous() \
+                or offsets.device != self.device:
+            raise ValueError("offsets: expected contiguous int64 [S + 1] on %s" % self.device)
+        for name, t in (("rows", rows), ("shift", shift)):
+            if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"{name}: expected contiguous int32 [M] on {self.device}")
+        S = offsets.shape[0] - 1
+        out = self.empty_ct(S) if out is None else out
+        _native.check(self.lib.pai_ct_segment_prod(self.h, _ptr(ct), ct.shape[0], int(tag), _ptr(rows), _ptr(shift), _ptr(offsets), S,
+                                                   _ptr(out), _stream(self.device)))
+        return out
+
     def ct_multiexp(self, ct: torch.Tensor, ct_inv: Optional[torch.Tensor], R: int, K: int, M: int, e: torch.Tensor,
                     ebits_max: int, sign: Optional[torch.Tensor]) -> torch.Tensor:
         """out[r*M + j] = prod_l base(r, l, j)^e[r, l, j] mod n^2 (pai_ct_multiexp); ct [R*K, W], e int32 [R, K, M, ew],
@@ -436,6 +454,8 @@ class PublicKeyHandle:
             raise _native.NativeError(_native.PAI_E_INVALID, "ct_invert: a ciphertext is not invertible modulo n^2")
         if v.value & 2:
             raise _native.NativeError(_native.PAI_E_INVALID, "ct_pow2_hint: max_delta was smaller than a shift of its batch")
+        if v.value & 4:
+            raise _native.NativeError(_native.PAI_E_INVALID, "ct_segment_prod: a member row was out of range or a shift negative")
 
     def ct_pow2_(self, ct: torch.Tensor, delta, max_delta: Optional[int] = None) -> torch.Tensor:
         """ct_i <- ct_i^(2^delta_i) in place for delta_i > 0.  delta: int32 device tensor, or a host numpy array (then the

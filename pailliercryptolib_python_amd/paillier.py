@@ -369,6 +369,83 @@ def _add_aligned(h: engine.PublicKeyHandle, ta: torch.Tensor, tb: torch.Tensor, 
     return res
 
 
+def _segment_ids(segment_ids, n: int, num_segments) -> torch.Tensor:
+    """segment_sum's argument checks: an integer array of shape (n,) or (n, F) (numpy or torch) -> int64 tensor [n, F] on its own
+    device.  Raises TypeError / ValueError before anything is launched for the segment sum."""
+    if isinstance(num_segments, (bool, np.bool_)) or not isinstance(num_segments, (int, np.integer)):
+        raise TypeError("segment_sum: num_segments must be an integer")
+    if num_segments <= 0:
+        raise ValueError("segment_sum: num_segments must be positive")
+    if isinstance(segment_ids, np.ndarray):
+        if segment_ids.dtype.kind not in "iu":
+            raise TypeError(f"segment_sum: segment_ids must have an integer dtype, got {segment_ids.dtype}")
+        if segment_ids.dtype == np.uint64 and segment_ids.size and int(segment_ids.max()) >= 1 << 63:
+            raise ValueError("segment_sum: segment id out of range")
+        ids = torch.from_numpy(np.ascontiguousarray(segment_ids).astype(np.int64))
+    elif isinstance(segment_ids, torch.Tensor):
+        if segment_ids.dtype.is_floating_point or segment_ids.dtype.is_complex or segment_ids.dtype == torch.bool:
+            raise TypeError(f"segment_sum: segment_ids must have an integer dtype, got {segment_ids.dtype}")
+        if segment_ids.dtype == getattr(torch, "uint64", None):
+            # ids >= 2^63 would wrap to negative (dropped) in int64: the same ValueError as for numpy ids
+            ids = segment_ids.detach().view(torch.int64)
+            if ids.numel() and bool((ids < 0).any()):
+                raise ValueError("segment_sum: segment id out of range")
+        else:
+            ids = segment_ids.detach().to(torch.int64)
+    else:
+        raise TypeError(f"segment_sum: segment_ids must be a numpy array or a torch tensor, got {type(segment_ids)}")
+    if ids.dim() not in (1, 2) or ids.shape[0] != n:
+        raise ValueError(f"segment_sum: segment_ids must have shape ({n},) or ({n}, F), got {tuple(ids.shape)}")
+    if ids.dim() == 1:
+        ids = ids.reshape(n, 1)
+    if ids.numel() and int(ids.max()) >= num_segments:
+        raise ValueError(f"segment_sum: segment id >= num_segments ({num_segments})")
+    return ids
+
+
+def _segment_plan(ids: torch.Tensor, expo: np.ndarray, num_segments: int):
+    """The member lists of segment_sum, built with torch on the ids' device (CPU tensors too).  ids: int64 [N, F] (< 0: the
+    (row, feature) pair is dropped); expo: the host exponents [N].  Segment f * K + id holds the rows i with ids[i, f] == id, sorted by
+    exponent (one stable sort on (segment, exponent); dropped pairs go to a sentinel segment after the last).  Returns
+    (rows int32 [N F], shift int32 [N F], offsets int64 [S + 1], seg_expo int64 [S]): the first offsets[S] entries of rows / shift
+    are the members, shift[j] = e_j - e_{j-1} inside a segment and 0 at its start — the Horner chain acc <- acc^(2^shift) * ct
+    then yields prod ct_i^(2^(E_s - e_i)) — and seg_expo = E_s, the largest member exponent (an empty segment: the smallest
+    exponent of the input, 0 for an empty input)."""
+    dev = ids.device
+    N, F = ids.shape
+    K = int(num_segments)
+    S = F * K
+    P = N * F
+    eh = np.asarray(expo, dtype=np.int64).reshape(-1)
+    lo = int(eh.min()) if N else 0
+    span = int(eh.max()) - lo + 1 if N else 1
+    expo = torch.from_numpy(eh).to(dev)
+    emin = torch.full((), lo, dtype=torch.int64, device=dev)
+    seg = ids + (torch.arange(F, device=dev, dtype=torch.int64) * K)[None, :]
+    seg = torch.where(ids >= 0, seg, torch.full_like(seg, S)).reshape(-1)
+    row = torch.arange(N, device=dev, dtype=torch.int64)[:, None].expand(N, F).reshape(-1)
+    e = expo[row] if P else torch.zeros(0, dtype=torch.int64, device=dev)
+    if P:
+        # one key (segment, exponent) where it fits 62 bits (the exponent span is small in practice), else two stable sorts:
+        # the same order
+        if (S + 1) * span < (1 << 62):
+            order = torch.argsort(seg * span + (e - lo), stable=True)
+        else:
+            o1 = torch.argsort(e, stable=True)
+            order = o1[torch.argsort(seg[o1], stable=True)]
+    else:
+        order = torch.zeros(0, dtype=torch.int64, device=dev)
+    seg_s, row_s, e_s = seg[order], row[order], e[order]
+    offsets = torch.searchsorted(seg_s, torch.arange(S + 1, device=dev, dtype=torch.int64))
+    shift = torch.zeros(P, dtype=torch.int64, device=dev)
+    if P > 1:
+        shift[1:] = torch.where(seg_s[1:] == seg_s[:-1], e_s[1:] - e_s[:-1], torch.zeros_like(e_s[1:]))
+    last = (offsets[1:] - 1).clamp(min=0)
+    nonempty = offsets[1:] > offsets[:-1]
+    seg_expo = torch.where(nonempty, e_s[last] if P else emin.expand(S), emin.expand(S))
+    return row_s.to(torch.int32), shift.to(torch.int32), offsets.contiguous(), seg_expo
+
+
 class PaillierEncryptedNumber:
     def __init__(self, public_key: PaillierPublicKey, ciphertext: ipclCipherText, exponents, length: int):
         """ipcl_python.py:249-270."""
@@ -803,6 +880,27 @@ class PaillierEncryptedNumber:
         """ipcl_python.py:746-762 (intended behaviour)."""
         out, e = self._aligned_tree(self._w, self._expo, 1)
         return self._wrap(out, [int(e[0])], 1)
+
+    def segment_sum(self, segment_ids, num_segments: int) -> "PaillierEncryptedNumber":
+        """Extension: sums by key — the encrypted histograms of SecureBoost-style training, H[f, b] = sum of the rows i with
+        segment_ids[i, f] == b.  segment_ids: an integer numpy array or torch tensor (any device) of shape (N,) or (N, F),
+        N = len(self); the result has F * num_segments elements, feature-major: element f * num_segments + b sums the rows with
+        segment_ids[i, f] == b.  A negative id drops that (row, feature) pair.  Exponents follow the addition rule: a segment's
+        exponent is the largest of its members' and member i is raised by ct^(2^(E_s - e_i)), so element s has the ciphertext and
+        exponent sum() gives on a container of exactly those members.  An empty segment gives the ciphertext 1 (E_raw(0), the
+        reference's padding value) at the smallest exponent of the input (0 for an empty input).
+        The outputs are NOT re-randomised (as sum()): an empty bin is recognisable as 1 — call .apply_obfuscator() on the result
+        before the histogram leaves the party.  Runs on the key's device (pai_ct_segment_prod: one Horner chain per segment and
+        chunk, one Montgomery product per member plus one per exponent step); no multi-GPU fan-out."""
+        n = self.__length
+        ids = _segment_ids(segment_ids, n, num_segments)
+        h = self._h()
+        t, dom = self.__ipclCipherText._raw()
+        if abs(dom) > ADDN_RPOW_SPAN - 2:
+            t, dom = h.ct_retag(t, dom, 0), 0
+        rows, shift, offsets, seg_expo = _segment_plan(ids.to(h.device), self._expo, int(num_segments))
+        out = h.ct_segment_prod(t, rows, shift, offsets, tag=dom)
+        return self._wrap(out, seg_expo.cpu().numpy().astype(np.int32), out.shape[0])
 
     def mean(self) -> "PaillierEncryptedNumber":
         return self.sum() / len(self)
