@@ -19,6 +19,7 @@ struct DecPadicParams {
     int nd;                      // base-R digits of a ciphertext
     uint4* wscratch;             // PADIC_WBUF: [NC][nslots] quotient digits of the digit-form entry and the exit
     int ct_words, u_words;
+    int sqr_kara;                // 36-limb primes: squarings by sqr_kara (MODE PADIC_LDS_K) instead of the row-wise sqr
 };
 
 // (A, B) <- Montgomery digit form of the packed integer `row` (row_words 32-bit words, any value < s^2 R-ish):
@@ -95,7 +96,9 @@ constexpr int PADIC_XLDS_FROM = 56;          // LDS-qualified digit accesses fro
 // 121.0 -> 112.7 ms per 65 536 at 3072-bit keys); at 72 limbs the same code LOSES (282.6 -> 383.4 ms: the nine specialised
 // a-parts next to the 160-register window no longer fit), so 4096-bit keys keep the plain rolled first half.
 constexpr int PADIC_SQR_SYM_MAX_NL = 56;
-constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1;
+// MODE PADIC_LDS_K: PADIC_LDS_M with the squarings in registers (mont_padic.hpp: sqr_kara, signed Karatsuba product columns,
+//                   NL even); the products keep the row-wise form and its LDS quotient-digit buffer.
+constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2;
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict__ u_out, int n,
@@ -105,7 +108,7 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
     const int which = blockIdx.y;
     const MontCtx* ctx = P.pr[which];
     // modulus and s - 1 from LDS (see kernels_padic_enc.hpp)
-    constexpr int LDS_DIGITS = MODE == PADIC_LDS_M ? 3 : 2;
+    constexpr int LDS_DIGITS = MODE == PADIC_WBUF ? 2 : 3;
     uint32_t* ldsn = lds + (BLOCK_THREADS / 64) * LDS_DIGITS * E::DIGIT_WORDS;
     for (int i = threadIdx.x; i < NL; i += BLOCK_THREADS) { ldsn[i] = ctx->n[i]; ldsn[NL + i] = P.pm1[which][i]; }
     __syncthreads();
@@ -128,12 +131,13 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
     const size_t nslots = (size_t)gridDim.x * gridDim.y * BLOCK_THREADS;
     const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * BLOCK_THREADS + threadIdx.x;
     // M: quotient digits of the first half of the product rule: an LDS digit buffer, or (PADIC_WBUF) a strided global column
-    const typename E::MBuf M = MODE != PADIC_LDS_M ? typename E::MBuf{P.wscratch + slot, nslots} : typename E::MBuf{B + E::NC * 64, 64};
+    const typename E::MBuf M = MODE == PADIC_WBUF ? typename E::MBuf{P.wscratch + slot, nslots} : typename E::MBuf{B + E::NC * 64, 64};
     auto SQR = [&]() {
         if constexpr (MODE == PADIC_WBUF) {
             if constexpr (NL <= PADIC_SQR_SYM_MAX_NL) E::sqr_sym_fused(A, B, nm, pm1, n0inv);
             else E::sqr_fused(A, B, nm, pm1, n0inv);
-        } else E::sqr(A, B, M, nm, pm1, n0inv);
+        } else if constexpr (MODE == PADIC_LDS_K) E::sqr_kara(A, B, nm, n0inv);
+        else E::sqr(A, B, M, nm, pm1, n0inv);
     };
     auto MUL = [&](auto&& csrc, auto&& dsrc) {
         if constexpr (MODE == PADIC_WBUF) E::mul_fused(A, B, csrc, dsrc, nm, pm1, n0inv);

@@ -685,6 +685,115 @@ struct Padic {
         store_digit(B, v);
         wave_lds_fence();
     }
+    // ---- (A, B) <- (A, B)^2 in registers, product columns by signed Karatsuba (NL even) --------------------------------
+    // Both digits are split at H = NL / 2 limbs, x = x0 + x1 B^H, y = y0 + y1 B^H (B = 2^29), and the limb-product column
+    // k of x y is assembled from three half-size coefficient vectors
+    //     X_k = P0_k + (P0 + P2 - D)_(k-H) + P2_(k-2H),   P0 = x0 y0,  P2 = x1 y1,  D = (x0 - x1)(y0 - y1),
+    // 3 H^2 limb products instead of NL^2 (3 H (H + 1) / 2 instead of NL (NL + 1) / 2 for a square).  The differences are
+    // 32-bit signed limbs in (-2^29, 2^29) and D is accumulated by signed multiply-adds: every partial sum is exact modulo
+    // 2^64 and X_k itself, the schoolbook column (at most NL products < 2^58), lies in [0, 2^64) — no carries, no
+    // normalisation.  P0_j is used at columns j and j + H, P2_j at j + H and j + 2H: each is computed once, at its
+    // first use, and stays live for H columns.
+    // The columns are consumed in order by the fused Montgomery reduction (as the product-scanning squaring of round 4):
+    // the product column goes through a carry stream of its own (cc) and only its low 29 bits, doubled for 2 a b, enter
+    // the reduction column with the quotient products, so neither 64-bit sum can wrap:  cc <= 2^63.2 + 2^35 and
+    // d <= NL 2^58 + 2^36 + 2^30.
+    // SECOND = false: w = (a^2 + m p) / R, quotient digits to mq.
+    // SECOND = true:  v = (2 a b - min + R p + m' p) / R  (R p - m = (R - 1 - m) + 1 + (p - 1) R; p - 1 = p with limb 0 less).
+    // w and v equal those of the row-wise sqr() exactly (the quotient digits are unique modulo R).
+    template <bool SECOND>
+    PAI_DEV static void kara_pass(uint32_t (&out)[NL], uint32_t (&mq)[NL], const uint32_t (&x)[NL], const uint32_t (&y)[NL],
+                                  const uint32_t (&min)[NL], const uint32_t* __restrict__ nm, uint32_t n0inv) {
+        static_assert(NL % 2 == 0, "even limb count");
+        constexpr int H = NL / 2, NP = 2 * H - 1;         // half-product coefficients 0 .. NP - 1
+        int32_t nx[H], dy[H];                             // nx = x1 - x0, dy = y0 - y1: nx * dy = -(x0 - x1)(y0 - y1)
+        uint32_t y2[NL];                                  // doubled limbs for the symmetric square
+        int32_t dy2[H];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            nx[i] = (int32_t)x[i + H] - (int32_t)x[i];
+            dy[i] = (int32_t)y[i] - (int32_t)y[i + H];
+            dy2[i] = dy[i] * 2;
+        }
+#pragma unroll
+        for (int i = 0; i < NL; ++i) y2[i] = y[i] << 1;
+        // half product of limbs [o, o + H) of x and y, coefficient j (a square: pairs i < l doubled, the diagonal once)
+        auto half = [&](int o, int j) -> uint64_t {
+            uint64_t s = 0;
+            const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+            for (int i = lo; i <= hi; ++i) {
+                const int l = j - i;
+                if (SECOND) s += (uint64_t)x[o + i] * y[o + l];
+                else if (i < l) s += (uint64_t)x[o + i] * y2[o + l];
+                else if (i == l) s += (uint64_t)x[o + i] * y[o + i];
+            }
+            return s;
+        };
+        uint64_t p0[NP], p2[NP];
+        uint64_t cc = 0, carry = 0;
+#pragma unroll
+        for (int k = 0; k < 2 * NL - 1; ++k) {
+            uint64_t t = 0;
+            if (k < NP) { p0[k] = half(0, k); t += p0[k]; }
+            if (k >= H && k - H < NP) {
+                const int j = k - H;
+                p2[j] = half(H, j);
+                t += p0[j] + p2[j];
+                const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                for (int i = lo; i <= hi; ++i) {
+                    const int l = j - i;
+                    if (SECOND) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
+                    else if (i < l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy2[l]);
+                    else if (i == l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[i]);
+                }
+            }
+            if (k >= 2 * H) t += p2[k - 2 * H];
+            const uint64_t c = t + cc;
+            cc = c >> RB;
+            const uint64_t lowc = SECOND ? (uint64_t)(((uint32_t)c & RMASK) << 1) : (uint64_t)((uint32_t)c & RMASK);
+            uint64_t d = lowc;
+            if (SECOND) d += k < NL ? (uint64_t)((RMASK - min[k]) + (k == 0 ? 1u : 0u)) : (uint64_t)(nm[k - NL] - (k == NL ? 1u : 0u));
+            const int lo = k < NL ? 0 : k - NL + 1, hi = k < NL ? k - 1 : NL - 1;
+            // the quotient products that do not wait for the previous column, then its carry and newest digit
+#pragma unroll
+            for (int i = lo; i <= hi; ++i)
+                if (i != k - 1) d += (uint64_t)mq[i] * nm[k - i];
+            d += carry;
+            if (k >= 1 && k - 1 < NL) d += (uint64_t)mq[k - 1] * nm[1];
+            if (k < NL) {
+                mq[k] = ((uint32_t)d * n0inv) & RMASK;
+                d += (uint64_t)mq[k] * nm[0];
+            } else {
+                out[k - NL] = (uint32_t)d & RMASK;
+            }
+            carry = d >> RB;
+        }
+        out[NL - 1] = (uint32_t)(carry + (SECOND ? (cc << 1) + nm[NL - 1] : cc)) & RMASK;
+    }
+    PAI_DEV static void load_digit(const uint4* x, uint32_t (&r)[NL]) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const uint4 t = ld(x, c);
+            r[4 * c] = t.x; r[4 * c + 1] = t.y; r[4 * c + 2] = t.z; r[4 * c + 3] = t.w;
+        }
+    }
+    PAI_DEV static void sqr_kara(uint4* A, uint4* B, const uint32_t* __restrict__ nm, uint32_t n0inv) {
+        uint32_t a[NL], m[NL], w[NL];
+        load_digit(A, a);
+        kara_pass<false>(w, m, a, a, m, nm, n0inv);
+        // a stays in registers for the second pass: w can take its place in LDS now
+        wave_lds_fence();
+        store_digit(A, w);
+        uint32_t b[NL], m2[NL], v[NL];
+        load_digit(B, b);
+        kara_pass<true>(v, m2, a, b, m, nm, n0inv);
+        wave_lds_fence();
+        store_digit(B, v);
+        wave_lds_fence();
+    }
+
     // (A, B) <- (A, B) * (C, D), the second operand's digits supplied per row block
     template <class CSrc, class DSrc>
     PAI_DEV static void mul(uint4* A, uint4* B, MBuf M, CSrc&& csrc, DSrc&& dsrc, const uint32_t* __restrict__ nm,

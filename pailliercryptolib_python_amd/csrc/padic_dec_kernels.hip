@@ -21,7 +21,7 @@ size_t padic_scratch_words(int nl, size_t blocks) { return nl <= 36 ? 0 : (size_
 // rows per block: 12 at 24 / 36 limbs (4-row blocks: 506.9 vs 477.8 ms per 2^20, profiles/r04/README.md), 8 at 56 / 72
 template <int NL, int U, int MODE>
 static void launch_padic(hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table) {
-    constexpr int bytes = (MODE == PADIC_LDS_M ? 3 : 2) * NL * BLOCK_THREADS * 4 + 2 * NL * 4;
+    constexpr int bytes = (MODE == PADIC_WBUF ? 2 : 3) * NL * BLOCK_THREADS * 4 + 2 * NL * 4;
     (void)hipFuncSetAttribute((const void*)k_dec_a_padic<NL, U, MODEXP_WINDOW, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     hipLaunchKernelGGL((k_dec_a_padic<NL, U, MODEXP_WINDOW, MODE>), dim3(gridx, 2), dim3(BLOCK_THREADS), bytes, s, P, ct, u_out, n,
                        reinterpret_cast<uint4*>(table));
@@ -30,7 +30,10 @@ bool launch_dec_a_padic(int nl, hipStream_t s, int gridx, const DecPadicParams& 
                         uint32_t* u_out, int n, uint32_t* table) {
     switch (nl) {
         case 24: launch_padic<24, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table); return true;
-        case 36: launch_padic<36, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table); return true;
+        case 36:
+            if (P.sqr_kara) launch_padic<36, 12, PADIC_LDS_K>(s, gridx, P, ct, u_out, n, table);
+            else launch_padic<36, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table);
+            return true;
         case 56: launch_padic<56, 8, PADIC_WBUF>(s, gridx, P, ct, u_out, n, table); return true;
         case 72: launch_padic<72, 8, PADIC_WBUF>(s, gridx, P, ct, u_out, n, table); return true;
         default: return false;

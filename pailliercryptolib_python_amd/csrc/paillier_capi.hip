@@ -369,6 +369,7 @@ struct ScopedKernelTimer {
 // particular path lives in two lists, read at every use (tests change them between calls):
 //   PAI_DISABLE="padic,pair,..."   engines / forms to leave out: padic (digit-pair engines: lane-group and wide fallbacks
 //                                  serve), pair, pair_ctmul, wide, gform (plain fixed-base tables), fb_chain, lat_dense, lat_enc_m1, lat_add_m1
+//                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
 //                                  segprod_chunk
