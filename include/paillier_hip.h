@@ -259,6 +259,21 @@ int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
 int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, const uint32_t* d_rows, const int32_t* d_shift,
                         const int64_t* d_offsets, size_t S, uint32_t* d_out, void* stream);
 
+/* Sparse multi-exponentiation behind PaillierEncryptedNumber.csr_matmul / csr_rmatmul and the scipy forms of @ (extension; no
+ * reference counterpart): T terms in segment order, d_out[s] = prod over the terms t = d_offsets[s] .. d_offsets[s+1] - 1 of
+ * B_t^(e_t) mod n^2, in the wire form (canonical residues); an empty segment gives 1.  B_t = d_ct[d_base[t]], or
+ * d_ct_inv[d_base[t]] when d_sign[t] != 0.  d_ct, d_ct_inv: [N][ct_words] wire form (d_ct_inv and d_sign both NULL or both
+ * given); d_base: int32 [T]; d_e: [T][e_words] little-endian exponent words of at most ebits_max bits; d_sign: uint8 [T];
+ * d_offsets: int64 [S + 1], nondecreasing, d_offsets[S] = T.  One power table per base (and sign), shared by all its terms;
+ * chunks of consecutive terms of a segment run one Straus chain each (PAI_TUNE smexp_chunk: the chunk length) and their partials
+ * are combined per segment as in pai_ct_segment_prod.  A base outside [0, N) is skipped, offsets that step back or leave [0, T]
+ * are clamped (those terms are dropped); either sets bit 3 of the handle's status word and never reads out of bounds.
+ * PAI_E_UNSUPPORTED: T >= 2^31, N >= 2^28, or the tables do not fit the device.  Synchronises `stream` once (the combine's
+ * sizes). */
+int pai_ct_sparse_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_ct_inv, size_t N, const int32_t* d_base,
+                           const uint32_t* d_e, int e_words, int ebits_max, const uint8_t* d_sign, size_t T, const int64_t* d_offsets,
+                           size_t S, uint32_t* d_out, void* stream);
+
 /* Exponent alignment, ipcl_python.py:570-741 (ct * 2^delta as ciphertext^(2^delta)):
  * for delta_i > 0: d_ct[i] <- d_ct[i]^(2^delta_i) mod n^2; other elements are left untouched.
  * Batches of >= 16384 elements (PAI_POW2_DIGIT_MIN) on keys up to 2048 bits read the largest shift back first (this
@@ -274,8 +289,10 @@ int pai_ct_pow2_hint(const pai_pubkey* pk, uint32_t* d_ct, const int32_t* d_delt
  * undefined); bit 1 — a pai_ct_pow2_hint call was given a max_delta below a shift of its batch on the digit-engine path
  * (batches >= PAI_POW2_DIGIT_MIN on keys up to 2048 bits, hints the digit path serves; the raised ciphertexts of that call are
  * then wrong — a hint outside that range runs the lane-group kernel, which is correct for any shift, and flags nothing); bit 2 —
- * a pai_ct_segment_prod call met a member row >= N (skipped) or a negative shift (taken as 0).  The Python layer computes its
- * hints from host arrays, uses pai_ct_invert_flag and builds its segment plans itself, so it never depends on this word. */
+ * a pai_ct_segment_prod call met a member row >= N (skipped) or a negative shift (taken as 0); bit 3 — a pai_ct_sparse_multiexp
+ * call met a base outside [0, N) (the term skipped) or segment offsets that step back or leave [0, T] (clamped; the terms they
+ * drop are skipped).  The Python layer computes its hints from host arrays, uses pai_ct_invert_flag and builds and checks its
+ * segment and term plans itself, so it never depends on this word. */
 int pai_pubkey_status(const pai_pubkey* pk, int* status_out, int clear, void* stream);
 
 

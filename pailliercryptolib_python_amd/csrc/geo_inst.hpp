@@ -203,6 +203,12 @@ struct GeoInst {
         set_lds((const void*)k_mexp<GX>, GX::LDS_BYTES);
         hipLaunchKernelGGL(k_mexp<GX>, dim3(grid), dim3(BLOCK_THREADS), GX::LDS_BYTES, s, c, P, table, e, sign, out, nlanes);
     }
+    static void smexp(hipStream_t s, int grid, const MontCtx* c, MexpParams P, SmexpArgs S, const uint32_t* table, const uint32_t* e,
+                      const uint8_t* sign, uint32_t* out, int nlanes) {
+        using GX = Geo<G::NLL, G::T, G::U, false>;
+        set_lds((const void*)k_smexp<GX>, GX::LDS_BYTES);
+        hipLaunchKernelGGL(k_smexp<GX>, dim3(grid), dim3(BLOCK_THREADS), GX::LDS_BYTES, s, c, P, S, table, e, sign, out, nlanes);
+    }
     static void modmul_msb(hipStream_t s, int grid, const MsbCtx* c, const uint32_t* a, const uint32_t* b, uint32_t* out, int n, int w32) {
         if constexpr (G::T <= 8) {
             // (rows per block: the geometry's own — 9 / 12 / 18 on 36 x 4 spill inside the row loop, /tmp probe of round 6)
@@ -217,7 +223,7 @@ struct GeoInst {
     static const GeoOps* ops() {
         static const GeoOps o = {G::NLL, G::T, G::U, G::NL, G::EPB, G::LDS_BYTES, 2 * G::LDS_WORDS * 4,
                                  &modmul, &modexp_fixed, &modexp_var, &modexp_var_win, &encrypt, &fb_expand, &dec_a, &dec_b, &pow2, &sq_chain, &add_aligned, &addn, &table_words, &pair_finish, &mexp_table, &mexp,
-                                 G::T <= 8 ? &modmul_msb : nullptr, &segprod};
+                                 G::T <= 8 ? &modmul_msb : nullptr, &segprod, &smexp};
         return &o;
     }
 };

@@ -57,6 +57,9 @@ struct GeoOps {
     void (*modmul_msb)(hipStream_t, int grid, const MsbCtx*, const uint32_t* a, const uint32_t* b, uint32_t* out, int n, int w32);
     // segment products (k_segprod): one Horner chain of gathered rows per output; rpow as for addn
     void (*segprod)(hipStream_t, int grid, const MontCtx*, SegArgs, int w32, const uint32_t* rpow);
+    // sparse multi-exponentiation (k_smexp): chunks of a term list over the tables of mexp_table, one partial per chunk
+    void (*smexp)(hipStream_t, int grid, const MontCtx*, MexpParams, SmexpArgs, const uint32_t* table, const uint32_t* e,
+                  const uint8_t* sign, uint32_t* out, int nlanes);
 };
 
 const GeoOps* geo_ops_36x1();
@@ -122,6 +125,8 @@ bool launch_ctmul_padic(int nl, hipStream_t s, int grid, const CtMulPadicParams&
 struct MexpPadicParams;
 bool launch_mexp_table_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* ct, const uint32_t* ct_inv, int nlanes);
 bool launch_mexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
+bool launch_smexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e,
+                        const uint8_t* sign, uint32_t* out, int nlanes);
 // g-factoring of a finished digit-form table (kernels_padic_enc.hpp): passes 1 and 2 over `count` entries in chunks of K
 bool padic_enc_gform_supported();
 bool launch_fb_g_prefix_padic(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K,

@@ -285,6 +285,37 @@ k_seg_chunk_scan(const int64_t* __restrict__ off, int S, int64_t C, int64_t* __r
     if (t == SEG_PLAN_THREADS - 1) cstart[S] = sum[t];
 }
 
+// clean[s] = max(clamp(off[0 .. s], 0, T)) for s <= S: the segment offsets of pai_ct_sparse_multiexp made nondecreasing and
+// bounded by the term count (a segment whose offsets step back or leave [0, T] loses those terms); any change sets bit 3 of *status
+__global__ void __launch_bounds__(SEG_PLAN_THREADS)
+k_smexp_offsets(const int64_t* __restrict__ off, int S, int64_t T, int64_t* __restrict__ clean, int* status) {
+    __shared__ int64_t mx[SEG_PLAN_THREADS];
+    const int t = threadIdx.x, n = S + 1, per = (n + SEG_PLAN_THREADS - 1) / SEG_PLAN_THREADS;
+    const int s0 = min(n, t * per), s1 = min(n, (t + 1) * per);
+    int64_t own = 0;
+    for (int s = s0; s < s1; ++s) {
+        const int64_t v = off[s] < 0 ? 0 : (off[s] > T ? T : off[s]);
+        own = v > own ? v : own;
+    }
+    mx[t] = own;
+    __syncthreads();
+    for (int d = 1; d < SEG_PLAN_THREADS; d <<= 1) {               // inclusive max-scan (Hillis-Steele)
+        const int64_t v = t >= d ? mx[t - d] : 0;
+        __syncthreads();
+        mx[t] = v > mx[t] ? v : mx[t];
+        __syncthreads();
+    }
+    int64_t run = t > 0 ? mx[t - 1] : 0;
+    bool bad = false;
+    for (int s = s0; s < s1; ++s) {
+        const int64_t v = off[s] < 0 ? 0 : (off[s] > T ? T : off[s]);
+        run = v > run ? v : run;
+        clean[s] = run;
+        bad |= run != off[s];
+    }
+    if (bad) atomicOr(status, 8);
+}
+
 // coff[k] (k <= U) = the first member of chunk k; chunks k >= cstart[S] are empty (coff = off[S])
 __global__ void __launch_bounds__(256)
 k_seg_chunk_expand(const int64_t* __restrict__ off, const int64_t* __restrict__ cstart, int S, int64_t C,

@@ -23,6 +23,14 @@ struct MexpParams {
     int R, K, M, chunk, nsigns, e_words, ebits_max, wbits, w32;
 };
 
+// the term list of a sparse multi-exponentiation (k_smexp / k_smexp_padic: pai_ct_sparse_multiexp)
+struct SmexpArgs {
+    const int32_t* base;         // [T] the table row (base ciphertext) of each term
+    const int64_t* coff;         // [chunks + 1] first term of each chunk, nondecreasing, coff[chunks] <= T
+    int* status;                 // the handle's sticky status word (bit 3: a base outside [0, nbases), skipped)
+    int nbases;
+};
+
 // Geometry of one kernel instance: NLL limbs per lane, T lanes per element, U rows per block,
 // NMLDS = the modulus slice is re-read from LDS during the q*n step instead of living in VGPRs.
 // M1 = "minus-one" Montgomery contexts (mont_dev.hpp: Rows::block_m1) — the wide-group latency kernels.

@@ -609,4 +609,79 @@ k_mexp(const MontCtx* __restrict__ ctx, MexpParams P, const uint32_t* __restrict
     }
 }
 
+// Sparse multi-exponentiation on the lane-group engine (pai_ct_sparse_multiexp; see k_smexp_padic in kernels_padic_enc.hpp):
+// one lane group per chunk k of terms t in [coff[k], coff[k + 1]) of one segment, the table row from base[t], the window bits
+// from e[t][e_words], the sign from sign[t]; the partial product leaves as a canonical residue out[k].  A base outside
+// [0, nbases) is skipped and sets bit 3 of *status.
+template <class G>
+__global__ void __launch_bounds__(BLOCK_THREADS, PAI_MEXP_WAVES(G))
+k_smexp(const MontCtx* __restrict__ ctx, MexpParams P, SmexpArgs S, const uint32_t* __restrict__ table, const uint32_t* __restrict__ e,
+        const uint8_t* __restrict__ sign, uint32_t* __restrict__ out, int nlanes) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int t = G::gl();
+    typename G::NM nm;
+    load_modulus<G>(nm, ctx, lds);
+    const uint32_t n0inv = ctx->n0inv;
+    const int W = P.wbits, NT = 1 << W;
+    const int nwin = (P.ebits_max + W - 1) / W;
+    const int tiles = (nlanes + G::EPB - 1) / G::EPB;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int idx = tile * G::EPB + G::elem();
+        const bool live = idx < nlanes;
+        const long long t0 = live ? S.coff[idx] : 0, t1 = live ? S.coff[idx + 1] : 0;
+        bool bad = false;
+        uint32_t x[G::NLL];
+        load_const_slice<G>(x, ctx->one);
+        bool started = false;                         // wave-uniform: only ones so far
+#pragma unroll 1
+        for (int wi = nwin - 1; wi >= 0; --wi) {
+            if (started) {
+#pragma unroll 1
+                for (int sq = 0; sq < W; ++sq) mm_square<G>(x, lds, nm, n0inv);
+            }
+            const int bit = wi * W, k = bit >> 5, sh = bit & 31;
+#pragma unroll 1
+            for (int li = 0; li < P.chunk; ++li) {
+                const long long tm = t0 + li;
+                const bool has = tm < t1;              // dead lanes: t0 == t1
+                int b = 0, d = 0;
+                if (has) {
+                    b = S.base[tm];
+                    const size_t eoff = (size_t)tm * P.e_words;
+                    uint64_t bits2 = k < P.e_words ? e[eoff + k] : 0u;
+                    if (k + 1 < P.e_words) bits2 |= (uint64_t)e[eoff + k + 1] << 32;
+                    const bool ok = (unsigned)b < (unsigned)S.nbases;
+                    bad |= !ok;
+                    d = ok ? (int)((uint32_t)(bits2 >> sh) & (uint32_t)(NT - 1)) : 0;
+                    b = ok ? b : 0;                    // lanes with d == 0 still read (entry 0 = one): of a row that exists
+                }
+                if (__any(d != 0)) {
+                    const int sg = (d != 0 && sign && P.nsigns > 1) ? (int)sign[tm] : 0;
+                    const uint32_t* ent = table + (((size_t)b * P.nsigns + sg) * NT + d) * G::NL + G::NLL * t;
+                    uint32_t y[G::NLL];
+                    if constexpr (G::NLL % 4 == 0) {                 // limb slices move as 16-byte vectors
+                        const uint4* e4 = reinterpret_cast<const uint4*>(ent);
+#pragma unroll
+                        for (int c = 0; c < G::NLL / 4; ++c) {
+                            const uint4 v = e4[c];
+                            y[4 * c] = v.x; y[4 * c + 1] = v.y; y[4 * c + 2] = v.z; y[4 * c + 3] = v.w;
+                        }
+                    } else {
+#pragma unroll
+                        for (int jj = 0; jj < G::NLL; ++jj) y[jj] = ent[jj];
+                    }
+                    mm_times<G>(x, y, lds, nm, n0inv);
+                    started = true;
+                }
+            }
+        }
+        uint32_t one[G::NLL];
+        set_plain_one<G>(one);
+        mm_times<G>(x, one, lds, nm, n0inv);
+        cond_sub<G::NLL, G::T>(x, nm);
+        if (live) store_elem<G>(x, out + (size_t)idx * P.w32, P.w32, lds);
+        if (live && t == 0 && bad && S.status) atomicOr(S.status, 8);
+    }
+}
+
 }  // namespace pai

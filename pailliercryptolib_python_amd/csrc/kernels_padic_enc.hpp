@@ -1054,4 +1054,127 @@ k_mexp_padic(MexpPadicParams P, const uint32_t* __restrict__ e, const uint8_t* _
     }
 }
 
+// ---- sparse multi-exponentiation (pai_ct_sparse_multiexp, extension): the term list of a sparse matrix product -----------------
+// The same Straus chain as k_mexp_padic over the tables of k_mexp_table_padic (one per base, shared by every term that names it),
+// but a lane takes one chunk of <= P.chunk consecutive terms t in [coff[k], coff[k + 1]) of ONE segment, its table row from
+// base[t], its exponent from e[t][e_words] and its sign from sign[t].  The partial product leaves as a canonical residue out[k]
+// (the combine step multiplies the chunks of a segment).  A base outside [0, nbases) is skipped and sets bit 3 of *status.
+template <int NL, int U>
+__global__ void __launch_bounds__(BLOCK_THREADS, 1)
+k_smexp_padic(MexpPadicParams P, SmexpArgs S, const uint32_t* __restrict__ e, const uint8_t* __restrict__ sign,
+              uint32_t* __restrict__ out, int nlanes) {
+    using E = Padic<NL, U, false>;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* ldsn = lds + (BLOCK_THREADS / 64) * 2 * E::DIGIT_WORDS;
+    for (int i = threadIdx.x; i < NL; i += BLOCK_THREADS) { ldsn[i] = P.nctx->n[i]; ldsn[NL + i] = P.nm1[i]; }
+    __syncthreads();
+    uint32_t sn[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) sn[j] = __builtin_amdgcn_readfirstlane(ldsn[j]);
+    const uint32_t* nm = sn;
+    const uint32_t* nm_lds = ldsn;
+    const uint32_t* nm1 = ldsn + NL;
+    const uint32_t n0inv = P.nctx->n0inv;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint4* A = reinterpret_cast<uint4*>(lds + wave * 2 * E::DIGIT_WORDS) + lane;
+    uint4* B = A + E::NC * 64;
+    const size_t nslots = (size_t)gridDim.x * BLOCK_THREADS;
+    const size_t slot = (size_t)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    const typename E::MBuf M{P.mscratch + slot, nslots};
+    const int W = P.wbits, NT = 1 << W;
+    const int nwin = (P.ebits_max + W - 1) / W;
+    const int tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int idx = tile * BLOCK_THREADS + threadIdx.x;
+        const bool live = idx < nlanes;
+        const long long t0 = live ? S.coff[idx] : 0, t1 = live ? S.coff[idx + 1] : 0;
+        bool bad = false;
+        wave_lds_fence();
+#pragma unroll 1
+        for (int c = 0; c < E::NC; ++c) {
+            E::st(A, c, make_uint4(P.one_dig[4 * c], P.one_dig[4 * c + 1], P.one_dig[4 * c + 2], P.one_dig[4 * c + 3]));
+            E::st(B, c, make_uint4(P.one_dig[NL + 4 * c], P.one_dig[NL + 4 * c + 1], P.one_dig[NL + 4 * c + 2], P.one_dig[NL + 4 * c + 3]));
+        }
+        wave_lds_fence();
+        bool started = false;                         // wave-uniform: nothing but ones so far, squarings can be skipped
+#pragma unroll 1
+        for (int wi = nwin - 1; wi >= 0; --wi) {
+            if (started) {
+#pragma unroll 1
+                for (int sq = 0; sq < W; ++sq) E::sqr_fused(A, B, nm, nm1, n0inv);
+            }
+            const int bit = wi * W, k = bit >> 5, sh = bit & 31;
+#pragma unroll 1
+            for (int li = 0; li < P.chunk; ++li) {
+                const long long t = t0 + li;
+                const bool has = t < t1;               // dead lanes: t0 == t1
+                int b = 0, d = 0;
+                if (has) {
+                    b = S.base[t];
+                    const size_t eoff = (size_t)t * P.e_words;
+                    uint64_t bits2 = k < P.e_words ? e[eoff + k] : 0u;
+                    if (k + 1 < P.e_words) bits2 |= (uint64_t)e[eoff + k + 1] << 32;
+                    const bool ok = (unsigned)b < (unsigned)S.nbases;
+                    bad |= !ok;
+                    d = ok ? (int)((uint32_t)(bits2 >> sh) & (uint32_t)(NT - 1)) : 0;
+                    b = ok ? b : 0;                    // lanes with d == 0 still read (entry 0 = one): of a row that exists
+                }
+                if (__any(d != 0)) {
+                    const int sg = (d != 0 && sign && P.nsigns > 1) ? (int)sign[t] : 0;
+                    const uint4* ent = P.table + (((size_t)b * P.nsigns + sg) * NT + d) * 2 * E::NC;
+                    auto from_ent = [&](int dg) {
+                        return [=](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                            for (int c = 0; c < E::UC; ++c) {
+                                const uint4 tv = ent[dg * E::NC + E::UC * blk + c];
+                                xv[4 * c] = tv.x; xv[4 * c + 1] = tv.y; xv[4 * c + 2] = tv.z; xv[4 * c + 3] = tv.w;
+                            }
+                        };
+                    };
+                    E::mul_fused(A, B, from_ent(0), from_ent(1), nm, nm1, n0inv);
+                    started = true;
+                }
+            }
+        }
+        // leave Montgomery form (times the plain pair (1, 0)), then ct = w + v n as one integer, canonical (as k_mexp_padic)
+        uint32_t w[NL], v[NL];
+        {
+            auto one = [&](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = 0;
+                if (blk == 0) xv[0] = 1;
+            };
+            auto zero = [&](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = 0;
+            };
+            E::mm1_mul(w, M, A, one, nm, n0inv);
+            E::mm2_mul(v, M, A, B, zero, one, nm, nm1, n0inv);
+        }
+        wave_lds_fence();
+        E::store_digit(B, v);
+        wave_lds_fence();
+        uint32_t hi[NL];
+        E::mul_plain(hi, A, w, B, [&](int blk, uint32_t (&xv)[U]) { E::digits_uniform(nm_lds, blk, xv); });
+        wave_lds_fence();
+        E::store_digit(B, hi);
+        wave_lds_fence();
+        cond_sub_2nl<E>(A, B, P.nsq);
+        cond_sub_2nl<E>(A, B, P.nsq);
+        if (live) {
+            uint32_t* orow = out + (size_t)idx * P.ct_words;
+#pragma unroll 1
+            for (int k2 = 0; k2 < P.ct_words; ++k2) {
+                const int j0 = (32 * k2) / RB, s0 = 32 * k2 - RB * j0;
+                uint64_t tv = (uint64_t)lds_limb<E>(A, B, j0) >> s0;
+                tv |= (uint64_t)lds_limb<E>(A, B, j0 + 1) << (RB - s0);
+                tv |= (uint64_t)lds_limb<E>(A, B, j0 + 2) << (2 * RB - s0);
+                orow[k2] = (uint32_t)tv;
+            }
+            if (bad && S.status) atomicOr(S.status, 8);
+        }
+        wave_lds_fence();
+    }
+}
+
 }  // namespace pai

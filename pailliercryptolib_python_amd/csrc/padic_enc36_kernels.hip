@@ -25,5 +25,9 @@ void enc36_mexp_table(hipStream_t s, int grid, const MexpPadicParams& P, const u
 void enc36_mexp(hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes) {
     L36::mexp(s, grid, P, e, sign, out, nlanes);
 }
+void enc36_smexp(hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e, const uint8_t* sign,
+                 uint32_t* out, int nlanes) {
+    L36::smexp(s, grid, P, S, e, sign, out, nlanes);
+}
 
 }  // namespace pai

@@ -79,5 +79,12 @@ bool launch_mexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P
     else return false;
     return true;
 }
+bool launch_smexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e,
+                        const uint8_t* sign, uint32_t* out, int nlanes) {
+    if (nl == 72) L72::smexp(s, grid, P, S, e, sign, out, nlanes);
+    else if (nl == 36) enc36_smexp(s, grid, P, S, e, sign, out, nlanes);
+    else return false;
+    return true;
+}
 
 }  // namespace pai

@@ -63,6 +63,11 @@ struct EncLaunch {
         (void)hipFuncSetAttribute((const void*)k_mexp_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
         hipLaunchKernelGGL((k_mexp_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, e, sign, out, nlanes);
     }
+    static void smexp(hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e, const uint8_t* sign,
+                      uint32_t* out, int nlanes) {
+        (void)hipFuncSetAttribute((const void*)k_smexp_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
+        hipLaunchKernelGGL((k_smexp_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, S, e, sign, out, nlanes);
+    }
     static void pow(hipStream_t s, int grid, const PowPadicParams& P, const uint32_t* base, uint32_t* out, int n) {
         (void)hipFuncSetAttribute((const void*)k_pow_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
         hipLaunchKernelGGL((k_pow_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, base, out, n);
@@ -84,5 +89,7 @@ void enc36_g_finish(hipStream_t s, int grid, const MontCtx* nctx, uint32_t* tabl
 void enc36_pow(hipStream_t s, int grid, const PowPadicParams& P, const uint32_t* base, uint32_t* out, int n);
 void enc36_mexp_table(hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* ct, const uint32_t* ct_inv, int nlanes);
 void enc36_mexp(hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
+void enc36_smexp(hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e, const uint8_t* sign,
+                 uint32_t* out, int nlanes);
 
 }  // namespace pai

@@ -372,7 +372,7 @@ struct ScopedKernelTimer {
 //                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
-//                                  segprod_chunk
+//                                  segprod_chunk, smexp_chunk
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -509,14 +509,16 @@ struct pai_pubkey {
     int pow_nops = 0;
     mutable DevBuf ctmul_table;        // per-slot window tables of k_ctmul_padic
     mutable DevBuf pow2_expo;          // one-bit exponents of pai_ct_pow2's digit-engine path
-    mutable DevBuf mexp_table, mexp_partial;   // power tables and partial products of pai_ct_multiexp
+    mutable DevBuf mexp_table, mexp_partial;   // power tables and partial products of pai_ct_multiexp (and pai_ct_sparse_multiexp)
+    mutable DevBuf smexp_plan;                 // segment offsets and chunk plan of pai_ct_sparse_multiexp
     mutable DevBuf seg_partial, seg_plan;      // chunk partials and chunk plans of pai_ct_segment_prod
     uint32_t* d_nsq_words = nullptr;   // n^2 as packed words (extended-GCD modulus)
     mutable DevBuf table, tmp;    // standard-scheme scratch
     mutable DevBuf inv_prod, inv_inv, inv_fail;
     // sticky device status word of the asynchronous calls (pai_pubkey_status): bit 0 = pai_ct_invert_async met a
     // ciphertext that is not a unit, bit 1 = a pai_ct_pow2_hint hint was smaller than a shift of its batch, bit 2 =
-    // pai_ct_segment_prod met a member row >= N or a negative shift
+    // pai_ct_segment_prod met a member row >= N or a negative shift, bit 3 = pai_ct_sparse_multiexp met a base >= N or segment
+    // offsets that step back or leave [0, T]
     mutable DevBuf status;
     mutable DevBuf prod_a, prod_b;     // ping-pong levels of pai_ct_prod
     // Product trees run on single Montgomery products (k_modmul MODMUL_MONT); level k of a tree holds true values
@@ -1124,6 +1126,7 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     pk->pow2_expo.release();
     pk->mexp_table.release();
     pk->mexp_partial.release();
+    pk->smexp_plan.release();
     pk->seg_partial.release();
     pk->seg_plan.release();
     if (pk->d_nsq_words) (void)hipFree(pk->d_nsq_words);
@@ -1179,6 +1182,7 @@ int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
         pk->pow2_expo.release();
         pk->mexp_table.release();
         pk->mexp_partial.release();
+        pk->smexp_plan.release();
         pk->seg_partial.release();
         pk->seg_plan.release();
         pk->inv_prod.release();

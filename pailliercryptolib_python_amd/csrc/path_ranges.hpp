@@ -173,6 +173,16 @@ static size_t segprod_chunk(size_t ncu, int epb, size_t members) {
     return std::max<size_t>(4, (members + want - 1) / want);
 }
 
+// ---- sparse multi-exponentiation --------------------------------------------------------------------------------------------------
+// PAI_TUNE smexp_chunk: terms per lane (or lane group) of pai_ct_sparse_multiexp (>= 1; tests force 1 / 2 / 3).  Default: as
+// pai_ct_multiexp, enough chunks to fill `want_lanes` lanes, the rest of the sharing goes into longer chunks (the squarings of a
+// window are shared by a chunk).
+static size_t smexp_chunk(size_t want_lanes, size_t terms) {
+    long long v;
+    if (knob_tune("smexp_chunk", &v) && v >= 1) return (size_t)v;
+    return std::max<size_t>(1, (terms + want_lanes - 1) / std::max<size_t>(1, want_lanes));
+}
+
 // ---- the switch points of one key, for tests and probes (pai_path_edges) --------------------------------------------------------
 // every batch size E at which the path of `op` (0 decrypt, 1 DJN encrypt, 2 ct x pt, 3 ct + ct) may change between N = E and
 // N = E + 1 on a device of ncu compute units (a superset: a path a key cannot take leaves its edge in the list)

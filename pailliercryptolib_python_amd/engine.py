@@ -403,6 +403,32 @@ class PublicKeyHandle:
                                                    _ptr(out), _stream(self.device)))
         return out
 
+    def ct_sparse_multiexp(self, ct: torch.Tensor, ct_inv: Optional[torch.Tensor], base: torch.Tensor, e: torch.Tensor, ebits_max: int,
+                           sign: Optional[torch.Tensor], offsets: torch.Tensor) -> torch.Tensor:
+        """out[s] = prod over the terms t = offsets[s] .. offsets[s+1]-1 of (ct or, sign[t] != 0, ct_inv)[base[t]]^e[t] mod n^2
+        (pai_ct_sparse_multiexp; empty segments give 1).  ct / ct_inv: wire form [N, W]; base: int32 [T]; e: int32 [T, ew];
+        sign: uint8 [T] or None; offsets: int64 [S + 1].  Raises NativeError(PAI_E_UNSUPPORTED) when the sizes are not served."""
+        self._chk(ct, self.ct_words, "ct")
+        T = base.shape[0]
+        if base.dtype != torch.int32 or base.dim() != 1 or not base.is_contiguous() or base.device != self.device:
+            raise ValueError(f"base: expected contiguous int32 [T] on {self.device}")
+        if e.dtype != torch.int32 or e.dim() != 2 or e.shape[0] != T or e.shape[1] < 1 or not e.is_contiguous() or e.device != self.device:
+            raise ValueError(f"e: expected contiguous int32 [T, ew] on {self.device}")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or not offsets.is_contiguous() \
+                or offsets.device != self.device:
+            raise ValueError("offsets: expected contiguous int64 [S + 1] on %s" % self.device)
+        if (sign is None) != (ct_inv is None):
+            raise ValueError("ct_sparse_multiexp: signs and inverses come together")
+        if sign is not None:
+            self._chk(ct_inv, self.ct_words, "ct_inv")
+            if sign.dtype != torch.uint8 or tuple(sign.shape) != (T,) or not sign.is_contiguous() or sign.device != self.device:
+                raise ValueError(f"sign: expected contiguous uint8 [T] on {self.device}")
+        S = offsets.shape[0] - 1
+        out = self.empty_ct(S)
+        _native.check(self.lib.pai_ct_sparse_multiexp(self.h, _ptr(ct), _ptr(ct_inv), ct.shape[0], _ptr(base), _ptr(e), e.shape[1],
+                                                      int(ebits_max), _ptr(sign), T, _ptr(offsets), S, _ptr(out), _stream(self.device)))
+        return out
+
     def ct_multiexp(self, ct: torch.Tensor, ct_inv: Optional[torch.Tensor], R: int, K: int, M: int, e: torch.Tensor,
                     ebits_max: int, sign: Optional[torch.Tensor]) -> torch.Tensor:
         """out[r*M + j] = prod_l base(r, l, j)^e[r, l, j] mod n^2 (pai_ct_multiexp); ct [R*K, W], e int32 [R, K, M, ew],
@@ -456,6 +482,9 @@ class PublicKeyHandle:
             raise _native.NativeError(_native.PAI_E_INVALID, "ct_pow2_hint: max_delta was smaller than a shift of its batch")
         if v.value & 4:
             raise _native.NativeError(_native.PAI_E_INVALID, "ct_segment_prod: a member row was out of range or a shift negative")
+        if v.value & 8:
+            raise _native.NativeError(_native.PAI_E_INVALID, "ct_sparse_multiexp: a base was out of range or the offsets were not a "
+                                                             "nondecreasing list in [0, T]")
 
     def ct_pow2_(self, ct: torch.Tensor, delta, max_delta: Optional[int] = None) -> torch.Tensor:
         """ct_i <- ct_i^(2^delta_i) in place for delta_i > 0.  delta: int32 device tensor, or a host numpy array (then the

@@ -446,6 +446,182 @@ def _segment_plan(ids: torch.Tensor, expo: np.ndarray, num_segments: int):
     return row_s.to(torch.int32), shift.to(torch.int32), offsets.contiguous(), seg_expo
 
 
+# ---- sparse matrix products (csr_matmul / csr_rmatmul): terms (output element s, base row b, plaintext weight v) -----------------
+# routes taken by the sparse products since import: "fast" = pai_ct_sparse_multiexp, "composite" = gather, * and segment_sum
+SPARSE_ROUTES = {"fast": 0, "composite": 0}
+SPARSE_EBITS_CAP = 128          # widest aligned exponent the fast route takes (as the dense multi-exponentiation)
+
+
+def _host_array(x, what: str) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bool or x.dtype.is_complex:
+            raise TypeError(f"{what} must not be {x.dtype}")
+        x = x.detach()
+        if x.dtype == getattr(torch, "uint64", None):
+            return x.cpu().view(torch.int64).numpy().view(np.uint64)
+        if x.dtype in (torch.bfloat16,):
+            x = x.to(torch.float32)
+        return x.cpu().numpy()
+    if isinstance(x, np.ndarray):
+        return x
+    if isinstance(x, (list, tuple)):
+        return np.asarray(x)
+    raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x)}")
+
+
+def _csr_args(indptr, indices, data, shape, length: int, rhs: bool):
+    """The argument checks of csr_rmatmul (rhs: A @ self, A of `shape` = (m, n), self n x k) and csr_matmul (self @ B, B of
+    `shape` = (n, k), self m x n): CSR arrays (numpy, or torch on any device) -> (indptr int64 [rows + 1], indices int64 [nnz],
+    data ndarray [nnz] of kind f / i / u, (m, n, k)), all on the CPU.  Raises before anything is launched: ValueError for
+    shapes (the dense @'s wording for a mismatch), indptr, indices, m = 0 or k = 0; NotImplementedError for a sparse operand
+    that is not 2-D; TypeError for bool, complex or object data."""
+    op = "__rmatmul__" if rhs else "__matmul__"
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 2:
+        raise NotImplementedError(f"PaillierEncryptedNumber.{op}: input ndim {len(shape)} not supported")
+    if shape[0] < 0 or shape[1] < 0:
+        raise ValueError(f"PaillierEncryptedNumber.{op}: negative matrix shape {shape}")
+    if rhs:
+        m, n = shape
+        if n == 0 or length % n != 0:
+            raise ValueError("PaillierEncryptedNumber.__rmatmul__: matrix multiplysize mismatch")
+        k = length // n
+    else:
+        n, k = shape
+        if n == 0 or length % n != 0:
+            raise ValueError("PaillierEncryptedNumber.__matmul__: matrix multiply size mismatch")
+        m = length // n
+    if m == 0 or k == 0:
+        raise ValueError(f"PaillierEncryptedNumber.{op}: empty product ({m} x {k})")
+    d = _host_array(data, "data")
+    if d.dtype.kind not in "fiu":
+        raise TypeError(f"PaillierEncryptedNumber.{op}: sparse data of dtype {d.dtype} is not supported")
+    ptr, idx = _host_array(indptr, "indptr"), _host_array(indices, "indices")
+    for name, a in (("indptr", ptr), ("indices", idx)):
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"PaillierEncryptedNumber.{op}: {name} must have an integer dtype, got {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"PaillierEncryptedNumber.{op}: {name} must be one-dimensional")
+    if d.ndim != 1 or d.shape[0] != idx.shape[0]:
+        raise ValueError(f"PaillierEncryptedNumber.{op}: data and indices must have the same length")
+    rows, cols = shape
+    if ptr.shape[0] != rows + 1:
+        raise ValueError(f"PaillierEncryptedNumber.{op}: indptr must have {rows + 1} entries, got {ptr.shape[0]}")
+    if (ptr.dtype == np.uint64 and int(ptr.max()) >= 1 << 63) or (idx.dtype == np.uint64 and idx.size and int(idx.max()) >= 1 << 63):
+        raise ValueError(f"PaillierEncryptedNumber.{op}: index out of range")
+    ptr64, idx64 = torch.from_numpy(ptr.astype(np.int64)), torch.from_numpy(idx.astype(np.int64))
+    if int(ptr64[0]) != 0 or int(ptr64[-1]) != idx64.shape[0] or bool((ptr64[1:] < ptr64[:-1]).any()):
+        raise ValueError(f"PaillierEncryptedNumber.{op}: indptr must rise from 0 to len(indices) = {idx64.shape[0]}")
+    if idx64.numel() and (int(idx64.min()) < 0 or int(idx64.max()) >= cols):
+        raise ValueError(f"PaillierEncryptedNumber.{op}: column index out of range [0, {cols})")
+    return ptr64, idx64, d, (m, n, k)
+
+
+def _sparse_weights(data: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(signed mantissas int64 [nnz], exponents int64 [nnz]) of the sparse weights, as ct * data encodes them: floats by their
+    53-bit mantissas (NaN / infinity raise ValueError / OverflowError as there), integers at exponent 0 — an int64 of -2^63
+    encodes as 0 (the codec's np.abs test), unsigned values above 2^63 - 1 raise ValueError."""
+    if data.dtype.kind == "f":
+        mant, expo = _fp.float64_mantissas(_fp.checked_float64(data.astype(np.float64)))
+        return mant.astype(np.int64), expo.astype(np.int64)
+    if data.dtype == np.uint64 and data.size and int(data.max()) >= 1 << 63:
+        raise ValueError("sparse weight out of the int64 range")
+    mant = data.astype(np.int64)
+    mant = np.where(mant == np.iinfo(np.int64).min, 0, mant)
+    return mant, np.zeros(mant.shape[0], dtype=np.int64)
+
+
+def _sparse_terms(indptr: torch.Tensor, indices: torch.Tensor, m: int, n: int, k: int, rhs: bool):
+    """The term list of a sparse product in segment order, on the device of `indptr` / `indices` (int64 CSR arrays).
+    rhs (A @ self, A m x n, self n x k): output (i, j) has the terms (base l k + j, weight A[i, l]) over the stored (i, l).
+    not rhs (self @ B, self m x n, B n x k): output (i, j) has the terms (base i n + l, weight B[l, j]) over the stored (l, j).
+    Returns (base int64 [T], widx int64 [T]: the stored entry of the weight, seg int64 [T], offsets int64 [S + 1]), S = m k."""
+    dev = indptr.device
+    nnz = indices.shape[0]
+    S = m * k
+    if rhs:
+        rowlen = indptr[1:] - indptr[:-1]                                                 # [m]
+        row = torch.repeat_interleave(torch.arange(m, device=dev), rowlen)                # [nnz]
+        p = torch.arange(nnz, device=dev)
+        j = torch.arange(k, device=dev)
+        # entry p of row i, column j of self: segment i k + j, position indptr[i] k + j len_i + (p - indptr[i])
+        pos = (indptr[row] * k + (p - indptr[row]))[:, None] + j[None, :] * rowlen[row][:, None]
+        T = nnz * k
+        base = torch.empty(T, dtype=torch.int64, device=dev)
+        widx = torch.empty(T, dtype=torch.int64, device=dev)
+        seg = torch.empty(T, dtype=torch.int64, device=dev)
+        pos = pos.reshape(-1)
+        base[pos] = (indices[:, None] * k + j[None, :]).reshape(-1)
+        widx[pos] = p[:, None].expand(nnz, k).reshape(-1)
+        seg[pos] = (row[:, None] * k + j[None, :]).reshape(-1)
+        del pos
+        offsets = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        offsets[:S] = (indptr[:-1, None] * k + j[None, :] * rowlen[:, None]).reshape(-1)
+        offsets[S] = T
+    else:
+        rowlen = indptr[1:] - indptr[:-1]                                                 # [n]
+        lrow = torch.repeat_interleave(torch.arange(n, device=dev), rowlen)              # the B row l of each entry
+        order = torch.argsort(indices, stable=True)                                        # column-major, rows ascending
+        col = indices[order]
+        colptr = torch.searchsorted(col, torch.arange(k + 1, device=dev))                 # [k + 1]
+        i = torch.arange(m, device=dev)
+        T = m * nnz
+        base = ((i * n)[:, None] + lrow[order][None, :]).reshape(-1)
+        widx = order[None, :].expand(m, nnz).reshape(-1)
+        seg = ((i * k)[:, None] + col[None, :]).reshape(-1)
+        offsets = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        offsets[:S] = ((i * nnz)[:, None] + colptr[None, :k]).reshape(-1)
+        offsets[S] = T
+    return base, widx, seg, offsets
+
+
+def _sparse_plan(base: torch.Tensor, widx: torch.Tensor, seg: torch.Tensor, mant: torch.Tensor, pexpo: torch.Tensor,
+                 expo: torch.Tensor, S: int, cap: int = SPARSE_EBITS_CAP):
+    """The exponents of the fast route.  Term t: total = e_b + p_v (expo[base], pexpo[widx]); E_s = the largest total of segment s
+    (an empty segment: the smallest total, 0 without terms); the term's exponent is |mant| << (E_s - total) as int32 words [T][ew]
+    and sign[t] = mant < 0.  Returns (e or None when the widest exponent exceeds `cap` bits, ebits, sign uint8 [T], seg_expo int64
+    [S]); only ebits is read back (one synchronisation)."""
+    dev = base.device
+    T = base.shape[0]
+    total = expo[base] + pexpo[widx]
+    lo = total.min() if T else torch.zeros((), dtype=torch.int64, device=dev)
+    seg_expo = lo.expand(S).clone().scatter_reduce_(0, seg, total, reduce="amax", include_self=False) if T else lo.expand(S).clone()
+    mt = mant[widx]
+    mag = mt.abs()
+    sign = (mt < 0).to(torch.uint8)
+    del mt
+    shift = torch.where(mag == 0, torch.zeros_like(total), seg_expo[seg] - total)
+    del total
+    bitlen = torch.frexp(mag.to(torch.float64))[1].to(torch.int64)                      # 0 for 0; may exceed by one near 2^63
+    ebits = max(1, int((bitlen + shift).max().item())) if T else 1
+    del bitlen
+    if ebits > cap:
+        return None, ebits, sign, seg_expo
+    ew = (ebits + 31) // 32
+    e = torch.empty((T, ew), dtype=torch.int32, device=dev)
+    m32 = 0xFFFFFFFF
+    for wi in range(ew):
+        pos = 32 * wi - shift                                                               # bit of mag at the word's bit 0
+        right = (mag >> pos.clamp(0, 63)) & m32
+        left = ((mag & m32) << (-pos).clamp(0, 31)) & m32
+        w = torch.where(pos >= 0, right, torch.where(pos > -32, left, torch.zeros_like(left)))
+        e[:, wi] = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        del pos, right, left, w
+    return e, ebits, sign, seg_expo
+
+
+def _scipy_sparse(x):
+    """x as CSR if it is a scipy sparse array / matrix (scipy is never imported here: an object of it implies it is loaded)."""
+    import sys
+
+    sp = sys.modules.get("scipy.sparse")
+    if sp is None or not sp.issparse(x):
+        return None
+    if len(x.shape) != 2:
+        raise NotImplementedError(f"PaillierEncryptedNumber: sparse input ndim {len(x.shape)} not supported")
+    return x.tocsr()
+
+
 class PaillierEncryptedNumber:
     def __init__(self, public_key: PaillierPublicKey, ciphertext: ipclCipherText, exponents, length: int):
         """ipcl_python.py:249-270."""
@@ -902,6 +1078,75 @@ class PaillierEncryptedNumber:
         out = h.ct_segment_prod(t, rows, shift, offsets, tag=dom)
         return self._wrap(out, seg_expo.cpu().numpy().astype(np.int32), out.shape[0])
 
+    def csr_rmatmul(self, indptr, indices, data, shape) -> "PaillierEncryptedNumber":
+        """Extension: A @ self for a plaintext sparse A given as CSR arrays (numpy, or torch on any device; no scipy needed) of
+        shape (m, n); self is n x k row-major, the result m x k row-major — the encrypted gradient X.T @ [[d]] of vertical
+        federated regression.  Output (i, j) is the library's sum of the products self[l k + j] * A[i, l] over the STORED (i, l)
+        (explicit zeros and duplicates count as terms): exactly the bits and exponent of gathering those rows, multiplying by the
+        weights (ct * data: floats by their mantissas, integers at exponent 0) and segment_sum — the exponent is the largest
+        e_b + p_v of its terms, an element without terms is the ciphertext 1 at the smallest term exponent of the call (0 when
+        there are no terms).  The outputs are NOT re-randomised (as sum()): call .apply_obfuscator() on the result before it
+        leaves the party.  Runs on the key's device (pai_ct_sparse_multiexp: one power table per ciphertext, one Straus chain per
+        chunk of terms); products it does not serve (aligned exponents above 128 bits) take the composite route."""
+        ptr, idx, d, (m, n, k) = _csr_args(indptr, indices, data, shape, len(self), True)
+        return self._sparse_product(ptr, idx, d, m, n, k, True)
+
+    def csr_matmul(self, indptr, indices, data, shape) -> "PaillierEncryptedNumber":
+        """Extension: self @ B for a plaintext sparse B given as CSR arrays of shape (n, k); self is m x n row-major, the result
+        m x k.  Output (i, j) sums self[i n + l] * B[l, j] over the stored (l, j), with the rules of csr_rmatmul."""
+        ptr, idx, d, (m, n, k) = _csr_args(indptr, indices, data, shape, len(self), False)
+        return self._sparse_product(ptr, idx, d, m, n, k, False)
+
+    def _sparse_product(self, indptr: torch.Tensor, indices: torch.Tensor, data: np.ndarray, m: int, n: int, k: int,
+                        rhs: bool) -> "PaillierEncryptedNumber":
+        mant, pexpo = _sparse_weights(data)
+        h = self._h()
+        dev = h.device
+        S = m * k
+        T = indices.shape[0] * (k if rhs else m)
+        base, widx, seg, offsets = _sparse_terms(indptr.to(dev), indices.to(dev), m, n, k, rhs)
+        e = None
+        if T < (1 << 31) and self.public_key.n.bit_length() > 66:
+            expo = torch.from_numpy(self._expo.astype(np.int64)).to(dev)
+            e, ebits, sign, seg_expo = _sparse_plan(base, widx, seg, torch.from_numpy(mant).to(dev), torch.from_numpy(pexpo).to(dev),
+                                                    expo, S)
+        if e is not None:
+            from . import _native
+
+            flags, inv = [], None
+            if bool((mant < 0).any()):
+                flags.append(h.new_flag())
+                inv = h.ct_invert(self._w, flag=flags[-1])
+            else:
+                sign = None
+            del seg, widx
+            try:
+                out = h.ct_sparse_multiexp(self._w, inv, base.to(torch.int32), e, ebits, sign, offsets)
+            except _native.NativeError as exc:
+                if exc.code != _native.PAI_E_UNSUPPORTED:
+                    raise
+            else:
+                SPARSE_ROUTES["fast"] += 1
+                return self._wrap(out, seg_expo.cpu().numpy().astype(np.int32), S, flags=flags)
+            base, widx, seg, offsets = _sparse_terms(indptr.to(dev), indices.to(dev), m, n, k, rhs)
+        return self._sparse_composite(base, widx, seg, data, S)
+
+    def _sparse_composite(self, base: torch.Tensor, widx: torch.Tensor, seg: torch.Tensor, data: np.ndarray, S: int):
+        """The defining route of the sparse products: gather the term rows, ct * weights, segment_sum."""
+        SPARSE_ROUTES["composite"] += 1
+        bh = base.cpu().numpy()
+        terms = self._wrap(self._w[base].contiguous(), self._expo[bh], bh.shape[0])
+        if bh.shape[0]:
+            w = data[widx.cpu().numpy()]
+            if w.dtype.kind == "f":
+                w = w.astype(np.float64)
+            else:
+                if w.dtype == np.uint64 and int(w.max()) >= 1 << 63:
+                    raise ValueError("sparse weight out of the int64 range")
+                w = w.astype(np.int64)
+            terms = terms * w
+        return terms.segment_sum(seg, S)
+
     def mean(self) -> "PaillierEncryptedNumber":
         return self.sum() / len(self)
 
@@ -1035,7 +1280,10 @@ class PaillierEncryptedNumber:
         return self._wrap(out, gmax.astype(np.int32), m * k, others=(prod,))
 
     def __matmul__(self, other: Union[np.ndarray, list]) -> "PaillierEncryptedNumber":
-        """ipcl_python.py:882-903."""
+        """ipcl_python.py:882-903.  Extension: a scipy sparse B (any format, 2-D) is self @ B by csr_matmul."""
+        sp = _scipy_sparse(other)
+        if sp is not None:
+            return self.csr_matmul(sp.indptr, sp.indices, sp.data, sp.shape)
         if len(self) % len(other) != 0:
             raise ValueError("PaillierEncryptedNumber.__matmul__: matrix multiply size mismatch")
         other = np.array(other)
@@ -1047,7 +1295,11 @@ class PaillierEncryptedNumber:
         return self.__matmul(other, m, n, k)
 
     def __rmatmul__(self, other: Union[np.ndarray, list]) -> "PaillierEncryptedNumber":
-        """ipcl_python.py:905-925."""
+        """ipcl_python.py:905-925.  Extension: a scipy sparse A (any format, 2-D) is A @ self by csr_rmatmul — also for
+        `A @ enc` with scipy on the left (scipy defers to this method: see __array__)."""
+        sp = _scipy_sparse(other)
+        if sp is not None:
+            return self.csr_rmatmul(sp.indptr, sp.indices, sp.data, sp.shape)
         other = np.array(other)
         if other.ndim not in (1, 2):
             raise NotImplementedError(f"PaillierEncryptedNumber.__rmatmul__: input ndim {other.ndim} not supported")
@@ -1063,6 +1315,13 @@ class PaillierEncryptedNumber:
 
     # keep numpy from broadcasting `ndarray @ PaillierEncryptedNumber` element-wise
     __array_ufunc__ = None
+
+    def __array__(self, dtype=None, copy=None):
+        """A 0-d object array holding self: numpy and scipy then treat the container as one opaque operand (scipy's `X @ enc`
+        returns NotImplemented and Python calls __rmatmul__) instead of walking __getitem__ element by element."""
+        a = np.empty((), dtype=object)
+        a[()] = self
+        return a
 
 
 class BNUtils:
