@@ -114,7 +114,8 @@ int pai_pubkey_info(const pai_pubkey* pk, int* key_bits, int* n_words, int* ct_w
 int pai_pubkey_table_info(const pai_pubkey* pk, size_t* table_bytes, int* window_bits, int* windows);
 /* The batch sizes at which this key's calls change kernel family on its device (csrc/path_ranges.hpp: every range is a number
  * of elements per compute unit times the device's CU count; PAI_LATENCY_MAX / PAI_LAT_ADD_MAX / PAI_TUNE overrides included):
- * op 0 = pai_decrypt, 1 = pai_encrypt (DJN), 2 = pai_ct_mul, 3 = pai_ct_add*.  An edge E separates N = E from N = E + 1.
+ * op 0 = pai_decrypt, 1 = pai_encrypt (DJN), 2 = pai_ct_mul, 3 = pai_ct_add*, 4 = pai_ct_pack (its edge counts OUTPUT rows).  An edge E
+ * separates N = E from N = E + 1.
  * Writes at most `cap` edges (ascending) and the full count.  For tests and probes that want to stand on both sides of a switch
  * (tests/test_gpu_path_edges.py); no reference counterpart. */
 int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* count);
@@ -315,6 +316,32 @@ int pai_fp_encode_i64(const pai_pubkey* pk, const int64_t* d_x, size_t N, uint32
 int pai_fp_encode_at(const pai_pubkey* pk, const void* d_x, int is_f64, size_t N, const int32_t* d_target, int target_bcast,
                      uint32_t* d_m, int32_t* d_expo, void* stream);
 int pai_fp_decode_i64(const pai_pubkey* pk, const uint32_t* d_m, size_t N, int64_t* d_mant, int32_t* d_flag, void* stream);
+
+/* ---- packed ciphertexts: k fixed-point slots of b bits per plaintext (extension; no reference counterpart) ---------------
+ * Layout of a packed batch of N elements at `slot_bits` b (8..128) and `slots` k >= 1 with k b <= bits(n) - 2: G = ceil(N / k)
+ * rows; element i lives in row i / k, slot i % k, bits [j b, (j + 1) b); the plaintext of row g is the signed integer
+ * P_g = sum_j m_(g k + j) 2^(b j) reduced modulo n, with signed mantissas -2^(b-1) <= m < 2^(b-1); unused tail slots hold 0.
+ * With the bias B = sum_(j<k) 2^(b-1) 2^(b j), Q = (residue + B) mod n < 2^(k b) and m_j = ((Q >> b j) & (2^b - 1)) - 2^(b-1).
+ * A layout outside these bounds is PAI_E_INVALID and launches nothing.
+ *
+ * pai_fp_pack: d_x = double[N] (is_f64) or int64[N]; mantissa = rint(x 2^exponent), ties to even (exact), or x << exponent;
+ * d_m: [G][n_words] residues of P_g.  *d_flag (one device word the caller zeroes) receives bit 0 for a mantissa with
+ * |m| >= 2^value_bits (1 <= value_bits <= b - 1), bit 1 for a NaN or an infinity; the rows are then undefined. */
+int pai_fp_pack(const pai_pubkey* pk, const void* d_x, int is_f64, size_t N, int exponent, int value_bits, int slot_bits, int slots,
+                uint32_t* d_m, int32_t* d_flag, void* stream);
+/* pai_fp_unpack: d_m: [G][n_words] residues; d_out: int64 [G k] mantissas for b <= 64, int64 [G k][2] = (low 64 bits as uint64,
+ * high 64 bits, signed) above; d_flag: int32 [G]: 0 ok, 1 overflow zone (Q >= 2^(k b)), 2 residue >= n (the row's mantissas are
+ * then undefined). */
+int pai_fp_unpack(const pai_pubkey* pk, const uint32_t* d_m, size_t G, int slot_bits, int slots, int64_t* d_out, int32_t* d_flag,
+                  void* stream);
+/* pai_ct_pack: packs N ciphertexts (equal exponents: the caller's bookkeeping) into G: d_out[g] = prod_j d_ct[g k + j]^(2^(b j))
+ * mod n^2, an encryption of P_g, in the wire form (canonical residues, not re-randomised).  d_ct: [N][ct_words] at domain tag `tag`
+ * (as pai_ct_segment_prod); d_out: [G][ct_words], must not alias d_ct.  One Horner chain acc <- acc^(2^b) * ct_j, j = k-1 ... 0,
+ * per output row — b squarings and one product per packed element.  Two routes with identical results: the level driver of
+ * pai_ct_segment_prod (the member list is written on the device; synchronises `stream` once, like that call), and, for keys up to
+ * 2048 bits, wire-form input and batches of more output rows than the pai_path_edges(op 4) edge, one chain per lane on base-n
+ * digit pairs (asynchronous; PAI_DISABLE=pack_padic leaves it out). */
+int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int slot_bits, int slots, uint32_t* d_out, void* stream);
 
 /* Obfuscator randomness, replacing upstream ipcl's per-element getRandomBN inside
  * PublicKey::encrypt (called at classes.cpp:57): d_r[N][r_words] <- ChaCha20 key stream (RFC 8439 block

@@ -24,9 +24,10 @@ from .paillier import (  # noqa: F401
     PaillierPrivateKey,
     PaillierPublicKey,
 )
+from .packed import PaillierPackedNumber  # noqa: F401
 
 __all__ = [
-    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "BNUtils",
+    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "PaillierPackedNumber", "BNUtils",
     "FixedPointNumber", "context", "hybridControl", "hybridMode",
 ]
 __version__ = "0.1.0"

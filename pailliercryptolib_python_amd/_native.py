@@ -90,6 +90,9 @@ PROTOTYPES = {
     "pai_fp_encode_i64": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp, voidp]),
     "pai_fp_encode_at": (C.c_int, [voidp, voidp, C.c_int, C.c_size_t, voidp, C.c_int, voidp, voidp, voidp]),
     "pai_fp_decode_i64": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp, voidp]),
+    "pai_fp_pack": (C.c_int, [voidp, voidp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, voidp, voidp, voidp]),
+    "pai_fp_unpack": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, voidp, voidp, voidp]),
+    "pai_ct_pack": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, C.c_int, voidp, voidp]),
     "pai_draw_r": (C.c_int, [voidp, voidp, voidp, C.c_uint32, C.c_size_t, voidp, voidp]),
     "pai_modulus_create": (C.c_int, [voidp, C.c_int, C.c_int, C.POINTER(voidp)]),
     "pai_modulus_destroy": (None, [voidp]),

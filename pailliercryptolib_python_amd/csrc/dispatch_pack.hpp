@@ -1,0 +1,133 @@
+// pai_fp_pack / pai_fp_unpack / pai_ct_pack: packed ciphertexts, k fixed-point slots of b bits per plaintext (kernels_pack.hpp).
+// (Part of the C-API translation unit: included by paillier_capi.hip inside extern "C", after dispatch_reduce.hpp.)
+#pragma once
+
+// the layout rule shared by the three calls: 8 <= b <= 128, k >= 1, k b <= bits(n) - 2
+static void require_pack_layout(const pai_pubkey* pk, int slot_bits, int slots) {
+    require(slot_bits >= 8 && slot_bits <= 128, "packed layout: slot_bits must lie in 8 .. 128");
+    require(slots >= 1 && (long long)slots * slot_bits <= (long long)hbn::bitlen(pk->n) - 2,
+            "packed layout: slots * slot_bits must not exceed bits(n) - 2");
+}
+
+int pai_fp_pack(const pai_pubkey* pk, const void* d_x, int is_f64, size_t N, int exponent, int value_bits, int slot_bits, int slots,
+                uint32_t* d_m, int32_t* d_flag, void* stream) {
+    return guarded([&] {
+        require(pk && d_x && d_m && d_flag, "NULL argument");
+        require_pack_layout(pk, slot_bits, slots);
+        require(value_bits >= 1 && value_bits + 1 <= slot_bits, "packed layout: value_bits must lie in 1 .. slot_bits - 1");
+        require(exponent > -(1 << 20) && exponent < (1 << 20), "exponent out of range");
+        if (N == 0) return;
+        DeviceScope scope_(pk->device);
+        const size_t G = (N + (size_t)slots - 1) / (size_t)slots;
+        const dim3 grid((unsigned)((G + 255) / 256)), block(256);
+        if (is_f64)
+            hipLaunchKernelGGL(k_fp_pack<true>, grid, block, 0, (hipStream_t)stream, d_x, pk->d_nexp, pk->n_words, N, exponent, value_bits,
+                               slot_bits, slots, d_m, G, d_flag);
+        else
+            hipLaunchKernelGGL(k_fp_pack<false>, grid, block, 0, (hipStream_t)stream, d_x, pk->d_nexp, pk->n_words, N, exponent, value_bits,
+                               slot_bits, slots, d_m, G, d_flag);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int pai_fp_unpack(const pai_pubkey* pk, const uint32_t* d_m, size_t G, int slot_bits, int slots, int64_t* d_out, int32_t* d_flag,
+                  void* stream) {
+    return guarded([&] {
+        require(pk && d_m && d_out && d_flag, "NULL argument");
+        require_pack_layout(pk, slot_bits, slots);
+        if (G == 0) return;
+        DeviceScope scope_(pk->device);
+        const dim3 grid((unsigned)((G + 255) / 256)), block(256);
+        if (slot_bits > 64)
+            hipLaunchKernelGGL(k_fp_unpack<true>, grid, block, 0, (hipStream_t)stream, d_m, pk->d_nexp, pk->n_words, G, slot_bits, slots,
+                               d_out, d_flag);
+        else
+            hipLaunchKernelGGL(k_fp_unpack<false>, grid, block, 0, (hipStream_t)stream, d_m, pk->d_nexp, pk->n_words, G, slot_bits, slots,
+                               d_out, d_flag);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// Row g of the output is the Horner chain acc <- acc^(2^b) * ct[g k + j], j = len_g - 1 ... 0.
+// Route A (every key size): the member list (rows, steps, chain offsets) is written on the device (k_pack_plan) and run by the
+// level driver of pai_ct_segment_prod — k-member chains are cut into chunks when there are too few of them to fill the device,
+// and the partials joined at shift b * (chunk length).
+// Route B (keys the base-n digit engine serves, wire-form input, pack_padic_min_rows chains or more): the rows are brought to
+// digit form once (k_mexp_table_padic at one window bit: entry 0 = one, entry 1 = the ciphertext), then one chain per lane with
+// digit-pair squarings (k_ct_pack_padic).  false: the digit forms do not fit the device (the caller takes route A).
+static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32_t* d_ct, size_t N, int slot_bits, int slots, size_t G,
+                                 uint32_t* d_out) {
+    const int pnl = pk->penc_nl;
+    const size_t table_bytes = N * 2 * 2 * (size_t)pnl * 4;
+    size_t mem_free = 0, mem_total = 0;
+    HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+    if (table_bytes > mem_total / 8 || table_bytes > mem_free + pk->mexp_table.bytes) return false;
+    OrderScope order_(pk->order, s);
+    pk->mexp_table.ensure(table_bytes);
+    MexpPadicParams Q;
+    Q.nctx = pk->nmod.d_ctx;
+    Q.nm1 = pk->d_nm1;
+    Q.nsq = pk->d_nsq29;
+    Q.kdig = pk->d_ct_kdig;
+    Q.one_dig = pk->d_one_dig;
+    Q.mscratch = reinterpret_cast<uint4*>(pk->d_mscratch);
+    Q.table = pk->mexp_table.as<uint4>();
+    Q.nd = pk->ct_nd;
+    Q.ct_words = pk->ct_words;
+    Q.R = 1; Q.K = (int)N; Q.M = 1; Q.chunk = slots; Q.nsigns = 1;
+    Q.e_words = 1; Q.ebits_max = 1; Q.by_rows = 0;
+    Q.wbits = 1;
+    {
+        const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
+        ScopedKernelTimer t("k_mexp_table", s);
+        if (!launch_mexp_table_padic(pnl, s, grid, Q, d_ct, nullptr, (int)N))
+            throw PaiError(PAI_E_INTERNAL, "no digit-form kernel for this limb count");
+        t.stop();
+        HIP_CHECK(hipGetLastError());
+    }
+    {
+        const size_t tiles = (G + BLOCK_THREADS - 1) / BLOCK_THREADS;
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
+        ScopedKernelTimer t("k_ct_pack_padic", s);
+        if (!launch_ct_pack_padic(pnl, s, grid, Q, (int)N, slots, slot_bits, d_out, (int)G))
+            throw PaiError(PAI_E_INTERNAL, "no pack kernel for this limb count");
+        t.stop();
+        HIP_CHECK(hipGetLastError());
+    }
+    order_.done();
+    return true;
+}
+
+int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int slot_bits, int slots, uint32_t* d_out, void* stream) {
+    return guarded([&] {
+        require(pk != nullptr, "NULL argument");
+        require_pack_layout(pk, slot_bits, slots);
+        require(N == 0 || (d_ct && d_out), "NULL argument");
+        require(std::abs(tag) <= RPOW_SPAN - 2, "pai_ct_pack: domain tag out of range");
+        require(N < ((size_t)1 << 31), "pai_ct_pack: too many rows for one call");
+        if (N == 0) return;
+        std::lock_guard<std::mutex> lk(pk->mu);
+        DeviceScope scope_(pk->device);
+        hipStream_t s = (hipStream_t)stream;
+        g_last_times.clear();
+        const size_t G = (N + (size_t)slots - 1) / (size_t)slots;
+        if (pk->penc_nl != 0 && tag == 0 && N < ((size_t)1 << 28) && !knob_disabled("pack_padic") &&
+            G >= pack_padic_min_rows((size_t)pk->dev.ncu) && ct_pack_padic_locked(pk, s, d_ct, N, slot_bits, slots, G, d_out))
+            return;
+        uint32_t* rows;
+        int32_t* shift;
+        int64_t* offsets;
+        {
+            OrderScope order_(pk->order, s);
+            pk->pack_plan.ensure((G + 1) * sizeof(int64_t) + N * 8);
+            offsets = pk->pack_plan.as<int64_t>();
+            rows = reinterpret_cast<uint32_t*>(offsets + G + 1);
+            shift = reinterpret_cast<int32_t*>(rows + N);
+            hipLaunchKernelGGL(k_pack_plan, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, N, slots, slot_bits, G, rows, shift, offsets);
+            HIP_CHECK(hipGetLastError());
+            order_.done();
+        }
+        segment_prod_locked(pk, s, d_ct, N, tag, rows, shift, offsets, G, d_out);
+    });
+}

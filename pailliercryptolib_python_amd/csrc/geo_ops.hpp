@@ -127,6 +127,8 @@ bool launch_mexp_table_padic(int nl, hipStream_t s, int grid, const MexpPadicPar
 bool launch_mexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
 bool launch_smexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e,
                         const uint8_t* sign, uint32_t* out, int nlanes);
+bool launch_ct_pack_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out,
+                          int nlanes);
 // g-factoring of a finished digit-form table (kernels_padic_enc.hpp): passes 1 and 2 over `count` entries in chunks of K
 bool padic_enc_gform_supported();
 bool launch_fb_g_prefix_padic(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K,

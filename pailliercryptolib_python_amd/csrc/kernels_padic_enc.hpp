@@ -1177,4 +1177,102 @@ k_smexp_padic(MexpPadicParams P, SmexpArgs S, const uint32_t* __restrict__ e, co
     }
 }
 
+// ---- packed ciphertexts (pai_ct_pack, extension): one Horner chain per lane on digit pairs ----------------------------------------
+// out[g] = prod_j ct[g k + j]^(2^(b j)) mod n^2 as the chain acc <- acc^(2^b) * ct_j, j = k-1 ... 0, over the digit forms that
+// k_mexp_table_padic wrote with wbits = 1 (entry 0 of a row = one, entry 1 = the ciphertext).  The squarings are Padic::sqr_fused
+// (3.5 NL^2 limb products against the 8 NL^2 of a Montgomery product modulo n^2 on lane groups).  The wave runs all k slots: a
+// slot a lane does not have (the ragged last chain, dead lanes) multiplies by entry 0, and squarings of one stay one.
+template <int NL, int U>
+__global__ void __launch_bounds__(BLOCK_THREADS, 1)
+k_ct_pack_padic(MexpPadicParams P, int nrows, int slots, int slot_bits, uint32_t* __restrict__ out, int nlanes) {
+    using E = Padic<NL, U, false>;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* ldsn = lds + (BLOCK_THREADS / 64) * 2 * E::DIGIT_WORDS;
+    for (int i = threadIdx.x; i < NL; i += BLOCK_THREADS) { ldsn[i] = P.nctx->n[i]; ldsn[NL + i] = P.nm1[i]; }
+    __syncthreads();
+    uint32_t sn[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) sn[j] = __builtin_amdgcn_readfirstlane(ldsn[j]);
+    const uint32_t* nm = sn;
+    const uint32_t* nm_lds = ldsn;
+    const uint32_t* nm1 = ldsn + NL;
+    const uint32_t n0inv = P.nctx->n0inv;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint4* A = reinterpret_cast<uint4*>(lds + wave * 2 * E::DIGIT_WORDS) + lane;
+    uint4* B = A + E::NC * 64;
+    const size_t nslots = (size_t)gridDim.x * BLOCK_THREADS;
+    const size_t slot = (size_t)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    const typename E::MBuf M{P.mscratch + slot, nslots};
+    const int tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int idx = tile * BLOCK_THREADS + threadIdx.x;
+        const bool live = idx < nlanes;
+        const long long r0 = (long long)(live ? idx : nlanes - 1) * slots;            // the chain's first row; r0 < nrows
+        const int len = live ? (int)min((long long)slots, (long long)nrows - r0) : 0;
+        wave_lds_fence();
+#pragma unroll 1
+        for (int c = 0; c < E::NC; ++c) {
+            E::st(A, c, make_uint4(P.one_dig[4 * c], P.one_dig[4 * c + 1], P.one_dig[4 * c + 2], P.one_dig[4 * c + 3]));
+            E::st(B, c, make_uint4(P.one_dig[NL + 4 * c], P.one_dig[NL + 4 * c + 1], P.one_dig[NL + 4 * c + 2], P.one_dig[NL + 4 * c + 3]));
+        }
+        wave_lds_fence();
+#pragma unroll 1
+        for (int t = slots - 1; t >= 0; --t) {
+            if (t < slots - 1) {
+#pragma unroll 1
+                for (int sq = 0; sq < slot_bits; ++sq) E::sqr_fused(A, B, nm, nm1, n0inv);
+            }
+            const bool has = t < len;
+            const uint4* ent = P.table + ((size_t)(r0 + (has ? t : 0)) * 2 + (has ? 1 : 0)) * 2 * E::NC;
+            auto from_ent = [&](int dg) {
+                return [=](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                    for (int c = 0; c < E::UC; ++c) {
+                        const uint4 tv = ent[dg * E::NC + E::UC * blk + c];
+                        xv[4 * c] = tv.x; xv[4 * c + 1] = tv.y; xv[4 * c + 2] = tv.z; xv[4 * c + 3] = tv.w;
+                    }
+                };
+            };
+            E::mul_fused(A, B, from_ent(0), from_ent(1), nm, nm1, n0inv);
+        }
+        // leave Montgomery form (times the plain pair (1, 0)), then ct = w + v n as one integer, canonical (as k_mexp_padic)
+        uint32_t w[NL], v[NL];
+        {
+            auto one = [&](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = 0;
+                if (blk == 0) xv[0] = 1;
+            };
+            auto zero = [&](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = 0;
+            };
+            E::mm1_mul(w, M, A, one, nm, n0inv);
+            E::mm2_mul(v, M, A, B, zero, one, nm, nm1, n0inv);
+        }
+        wave_lds_fence();
+        E::store_digit(B, v);
+        wave_lds_fence();
+        uint32_t hi[NL];
+        E::mul_plain(hi, A, w, B, [&](int blk, uint32_t (&xv)[U]) { E::digits_uniform(nm_lds, blk, xv); });
+        wave_lds_fence();
+        E::store_digit(B, hi);
+        wave_lds_fence();
+        cond_sub_2nl<E>(A, B, P.nsq);
+        cond_sub_2nl<E>(A, B, P.nsq);
+        if (live) {
+            uint32_t* orow = out + (size_t)idx * P.ct_words;
+#pragma unroll 1
+            for (int k2 = 0; k2 < P.ct_words; ++k2) {
+                const int j0 = (32 * k2) / RB, s0 = 32 * k2 - RB * j0;
+                uint64_t tv = (uint64_t)lds_limb<E>(A, B, j0) >> s0;
+                tv |= (uint64_t)lds_limb<E>(A, B, j0 + 1) << (RB - s0);
+                tv |= (uint64_t)lds_limb<E>(A, B, j0 + 2) << (2 * RB - s0);
+                orow[k2] = (uint32_t)tv;
+            }
+        }
+        wave_lds_fence();
+    }
+}
+
 }  // namespace pai

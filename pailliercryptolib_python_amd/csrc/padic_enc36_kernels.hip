@@ -29,5 +29,8 @@ void enc36_smexp(hipStream_t s, int grid, const MexpPadicParams& P, const SmexpA
                  uint32_t* out, int nlanes) {
     L36::smexp(s, grid, P, S, e, sign, out, nlanes);
 }
+void enc36_ct_pack(hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out, int nlanes) {
+    L36::ct_pack(s, grid, P, nrows, slots, slot_bits, out, nlanes);
+}
 
 }  // namespace pai

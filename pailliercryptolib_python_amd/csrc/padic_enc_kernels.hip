@@ -86,5 +86,12 @@ bool launch_smexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& 
     else return false;
     return true;
 }
+bool launch_ct_pack_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out,
+                          int nlanes) {
+    if (nl == 72) L72::ct_pack(s, grid, P, nrows, slots, slot_bits, out, nlanes);
+    else if (nl == 36) enc36_ct_pack(s, grid, P, nrows, slots, slot_bits, out, nlanes);
+    else return false;
+    return true;
+}
 
 }  // namespace pai

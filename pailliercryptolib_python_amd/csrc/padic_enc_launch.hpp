@@ -68,6 +68,10 @@ struct EncLaunch {
         (void)hipFuncSetAttribute((const void*)k_smexp_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
         hipLaunchKernelGGL((k_smexp_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, S, e, sign, out, nlanes);
     }
+    static void ct_pack(hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out, int nlanes) {
+        (void)hipFuncSetAttribute((const void*)k_ct_pack_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
+        hipLaunchKernelGGL((k_ct_pack_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, nrows, slots, slot_bits, out, nlanes);
+    }
     static void pow(hipStream_t s, int grid, const PowPadicParams& P, const uint32_t* base, uint32_t* out, int n) {
         (void)hipFuncSetAttribute((const void*)k_pow_padic<NL, U>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES2);
         hipLaunchKernelGGL((k_pow_padic<NL, U>), dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, base, out, n);
@@ -91,5 +95,6 @@ void enc36_mexp_table(hipStream_t s, int grid, const MexpPadicParams& P, const u
 void enc36_mexp(hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
 void enc36_smexp(hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e, const uint8_t* sign,
                  uint32_t* out, int nlanes);
+void enc36_ct_pack(hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out, int nlanes);
 
 }  // namespace pai

@@ -20,6 +20,7 @@
 #include "kernels_padic_enc.hpp"
 #include "kernels_pair.hpp"
 #include "kernels_codec.hpp"
+#include "kernels_pack.hpp"
 #include "kernels_declat.hpp"
 
 using namespace pai;
@@ -369,10 +370,11 @@ struct ScopedKernelTimer {
 // particular path lives in two lists, read at every use (tests change them between calls):
 //   PAI_DISABLE="padic,pair,..."   engines / forms to leave out: padic (digit-pair engines: lane-group and wide fallbacks
 //                                  serve), pair, pair_ctmul, wide, gform (plain fixed-base tables), fb_chain, lat_dense, lat_enc_m1, lat_add_m1
-//                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns)
+//                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns),
+//                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
-//                                  segprod_chunk, smexp_chunk
+//                                  segprod_chunk, smexp_chunk, pack_padic_min
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -512,6 +514,7 @@ struct pai_pubkey {
     mutable DevBuf mexp_table, mexp_partial;   // power tables and partial products of pai_ct_multiexp (and pai_ct_sparse_multiexp)
     mutable DevBuf smexp_plan;                 // segment offsets and chunk plan of pai_ct_sparse_multiexp
     mutable DevBuf seg_partial, seg_plan;      // chunk partials and chunk plans of pai_ct_segment_prod
+    mutable DevBuf pack_plan;                  // member list of pai_ct_pack (rows, steps, chain offsets)
     uint32_t* d_nsq_words = nullptr;   // n^2 as packed words (extended-GCD modulus)
     mutable DevBuf table, tmp;    // standard-scheme scratch
     mutable DevBuf inv_prod, inv_inv, inv_fail;
@@ -1129,6 +1132,7 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     pk->smexp_plan.release();
     pk->seg_partial.release();
     pk->seg_plan.release();
+    pk->pack_plan.release();
     if (pk->d_nsq_words) (void)hipFree(pk->d_nsq_words);
     if (pk->d_tree_c) (void)hipFree(pk->d_tree_c);
     if (pk->d_tree_fix) (void)hipFree(pk->d_tree_fix);
@@ -1185,6 +1189,7 @@ int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
         pk->smexp_plan.release();
         pk->seg_partial.release();
         pk->seg_plan.release();
+        pk->pack_plan.release();
         pk->inv_prod.release();
         pk->inv_inv.release();
         pk->prod_a.release();
@@ -1301,7 +1306,7 @@ int pai_draw_r(const pai_pubkey* pk, const uint32_t* h_key8, const uint32_t* h_n
 
 int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* count) {
     return guarded([&] {
-        require(pk && count && op >= 0 && op <= 3 && (edges || cap == 0), "bad arguments");
+        require(pk && count && op >= 0 && op <= 4 && (edges || cap == 0), "bad arguments");
         const std::vector<size_t> e = path_edges(op, pk->key_bits, (size_t)pk->dev.ncu);
         *count = (int)e.size();
         for (int i = 0; i < (int)e.size() && i < cap; ++i) edges[i] = e[(size_t)i];
@@ -1312,6 +1317,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_ctmul.hpp"
 #include "dispatch_add.hpp"
 #include "dispatch_reduce.hpp"
+#include "dispatch_pack.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

@@ -183,8 +183,21 @@ static size_t smexp_chunk(size_t want_lanes, size_t terms) {
     return std::max<size_t>(1, (terms + want_lanes - 1) / std::max<size_t>(1, want_lanes));
 }
 
+// ---- packed ciphertexts -------------------------------------------------------------------------------------------------------------
+// pai_ct_pack on keys the digit engine serves: from this many OUTPUT rows (chains) on, one chain per lane on digit pairs
+// (k_ct_pack_padic); below, the k_segprod levels, which cut a chain into chunks and so fill the device with few chains.  A lane's
+// chain takes the same time however many lanes run, the levels' time grows with the rows.  Measured at 2048-bit keys, 64-bit slots,
+// k = 31, 256 CUs (tools/pack_time.py route_sweep, ms levels / digit pairs): 54 / 109 at 2 048 rows, 69 / 110 at 8 192, 84 / 111 at
+// 16 384, 167 / 112 at 24 576, 185 / 115 at 33 825 — the hand-over sits at 9/32 of the device's lanes (18 432 rows on 256 CUs).
+// PAI_TUNE pack_padic_min overrides (0 = every batch), PAI_DISABLE=pack_padic leaves the digit route out.
+static size_t pack_padic_min_rows(size_t ncu) {
+    long long v;
+    if (knob_tune("pack_padic_min", &v) && v >= 0) return (size_t)v;
+    return std::max<size_t>(1, ncu * (size_t)BLOCK_THREADS * 9 / 32);
+}
+
 // ---- the switch points of one key, for tests and probes (pai_path_edges) --------------------------------------------------------
-// every batch size E at which the path of `op` (0 decrypt, 1 DJN encrypt, 2 ct x pt, 3 ct + ct) may change between N = E and
+// every batch size E at which the path of `op` (0 decrypt, 1 DJN encrypt, 2 ct x pt, 3 ct + ct, 4 pai_ct_pack: E counts OUTPUT rows) may change between N = E and
 // N = E + 1 on a device of ncu compute units (a superset: a path a key cannot take leaves its edge in the list)
 static std::vector<size_t> path_edges(int op, int key_bits, size_t ncu) {
     std::vector<size_t> e;
@@ -204,6 +217,9 @@ static std::vector<size_t> path_edges(int op, int key_bits, size_t ncu) {
     case 3:
         e = {lat_add_max(ncu), 2 * lat_add_max(ncu), 4 * lat_add_max(ncu), (size_t)lat_add_wire_scale(key_bits) * lat_add_max(ncu),
              pow2_digit_min_elements(ncu) - 1};
+        break;
+    case 4:
+        e = {pack_padic_min_rows(ncu) - 1};
         break;
     default:
         break;

@@ -550,6 +550,44 @@ class PublicKeyHandle:
         _native.check(self.lib.pai_fp_decode_i64(self.h, _ptr(m), m.shape[0], _ptr(mant), _ptr(flag), _stream(self.device)))
         return mant, flag
 
+    # -- packed plaintexts: k slots of b bits per residue (packed.py; include/paillier_hip.h "packed ciphertexts") ----
+    def fp_pack(self, x: torch.Tensor, exponent: int, value_bits: int, slot_bits: int, slots: int):
+        """float64[N] or int64[N] on the device -> (residues int32[ceil(N / slots), n_words], flag int32[1]); flag bit 0: a
+        mantissa with |m| >= 2^value_bits, bit 1: NaN / infinity (pai_fp_pack)."""
+        if x.dtype not in (torch.float64, torch.int64) or x.dim() != 1 or not x.is_contiguous() or x.device != self.device:
+            raise ValueError("x: expected contiguous float64 / int64 [N] on %s" % self.device)
+        if slots < 1:
+            raise ValueError("slots: expected a positive count")
+        m = self.empty_pt((x.shape[0] + slots - 1) // slots)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.pai_fp_pack(self.h, _ptr(x), 1 if x.dtype == torch.float64 else 0, x.shape[0], int(exponent), int(value_bits),
+                                           int(slot_bits), int(slots), _ptr(m), _ptr(flag), _stream(self.device)))
+        return m, flag
+
+    def fp_unpack(self, m: torch.Tensor, slot_bits: int, slots: int):
+        """residues [G, n_words] -> (mantissas int64 [G * slots] for slot_bits <= 64, else int64 [G * slots, 2] = (low 64 bits,
+        high 64 bits signed); flags int32 [G]: 0 ok, 1 overflow zone, 2 residue >= n) (pai_fp_unpack)."""
+        self._chk(m, self.n_words, "m")
+        if slots < 1:
+            raise ValueError("slots: expected a positive count")
+        shape = (m.shape[0] * slots, 2) if slot_bits > 64 else (m.shape[0] * slots,)
+        out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        flag = torch.empty((m.shape[0],), dtype=torch.int32, device=self.device)
+        _native.check(self.lib.pai_fp_unpack(self.h, _ptr(m), m.shape[0], int(slot_bits), int(slots), _ptr(out), _ptr(flag),
+                                             _stream(self.device)))
+        return out, flag
+
+    def ct_pack(self, ct: torch.Tensor, slot_bits: int, slots: int, tag: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[N, W] rows at domain tag `tag` -> [ceil(N / slots), W] wire form: out[g] = prod_j ct[g slots + j]^(2^(slot_bits j))
+        mod n^2 (pai_ct_pack).  Synchronises the current stream once (the plan's sizes)."""
+        self._chk(ct, self.ct_words, "ct")
+        if slots < 1:
+            raise ValueError("slots: expected a positive count")
+        out = self.empty_ct((ct.shape[0] + slots - 1) // slots) if out is None else out
+        _native.check(self.lib.pai_ct_pack(self.h, _ptr(ct), ct.shape[0], int(tag), int(slot_bits), int(slots), _ptr(out),
+                                           _stream(self.device)))
+        return out
+
     def draw_r(self, n: int, key: bytes, nonce: bytes, counter0: int = 0) -> torch.Tensor:
         """Obfuscator randomness on the device: ChaCha20 key stream under ``key`` (32 bytes, from the OS CSPRNG) and
         ``nonce`` (12 bytes).  DJN keys: r < 2^randbits.  Standard keys: rows of bits(n) random bits (candidates; the

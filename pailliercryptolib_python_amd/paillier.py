@@ -100,6 +100,18 @@ class PaillierPublicKey:
     def raw_encrypt(self, plaintext: Union[np.ndarray, list, int, float]) -> "PaillierEncryptedNumber":
         return self.encrypt(plaintext, apply_obfuscator=False)
 
+    def encrypt_packed(self, values, *, exponent: int, value_bits: int, slot_bits: int, slots: Optional[int] = None,
+                       apply_obfuscator: bool = True) -> "PaillierPackedNumber":
+        """Extension (packed.py): `values` (a 1-D float64 / int64 array or list) as ceil(N / slots) ciphertexts that hold `slots`
+        fixed-point values each — slots-fold fewer encryptions, decryptions and bytes.  Mantissas are rint(x 2^exponent) (ties to
+        even) for floats, x << exponent for integers (exponent >= 0); a mantissa with |m| >= 2^value_bits, NaN or infinity is a
+        ValueError.  slots: default the largest count with slots * slot_bits <= bits(n) - 2.  Encoding and packing run on the
+        device (pai_fp_pack), then the usual encryption."""
+        from . import packed as _packed
+
+        return _packed.encrypt_packed(self, values, exponent=exponent, value_bits=value_bits, slot_bits=slot_bits, slots=slots,
+                                      apply_obfuscator=apply_obfuscator)
+
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
         exponents (pai_fp_encode_at: the plaintext side of ct + plaintext, see encrypt's _align_to), or None when the batch
@@ -301,6 +313,31 @@ class PaillierPrivateKey:
         else:
             ret = _fp.decode_array(words, encrypted_number._expo, self.__n, self.__max_int)
         return ret if len(encrypted_number) > 1 else ret[0]
+
+    def _decrypt_packed(self, p: "PaillierPackedNumber"):
+        from . import packed as _packed
+
+        if not isinstance(p, _packed.PaillierPackedNumber):
+            raise TypeError("decrypt_packed: expected a PaillierPackedNumber")
+        if p.public_key.n != self.__n:
+            raise ValueError("PaillierPrivateKey.decrypt_packed: Public key mismatch")
+        return _packed._decrypt_fields(self.prikey.decrypt_words, self.prikey._pk.handle, p)
+
+    def decrypt_packed(self, p: "PaillierPackedNumber") -> np.ndarray:
+        """Extension (packed.py): the N values of a packed container as a float64 ndarray — ceil(N / slots) decryptions, the
+        slots taken apart on the device (pai_fp_unpack).  Exact whenever |mantissa| < 2^53.  A slot that left its bits raises
+        OverflowError, a residue >= n the codec's "corrupted number" ValueError."""
+        from . import packed as _packed
+
+        m, wide = self._decrypt_packed(p)
+        return _packed.mantissas_to_float64(m, wide, p.exponent)
+
+    def decrypt_packed_mantissas(self, p: "PaillierPackedNumber") -> List[int]:
+        """Extension: the N signed mantissas (value = mantissa 2^-exponent) as Python ints, exact."""
+        from . import packed as _packed
+
+        m, wide = self._decrypt_packed(p)
+        return _packed.mantissas_to_ints(m, wide)
 
     def decrypt_to_numpy(self, encrypted_number: "PaillierEncryptedNumber") -> np.ndarray:
         """Extension: the decoded values as a float64 ndarray without per-element Python objects."""
@@ -1077,6 +1114,18 @@ class PaillierEncryptedNumber:
         rows, shift, offsets, seg_expo = _segment_plan(ids.to(h.device), self._expo, int(num_segments))
         out = h.ct_segment_prod(t, rows, shift, offsets, tag=dom)
         return self._wrap(out, seg_expo.cpu().numpy().astype(np.int32), out.shape[0])
+
+    def pack(self, *, slot_bits: int, value_bits: int, exponent: Optional[int] = None, slots: Optional[int] = None
+             ) -> "PaillierPackedNumber":
+        """Extension (packed.py): these N ciphertexts as ceil(N / slots) packed ones.  Every element is first brought to
+        `exponent` (default: the container's largest; one below it is a ValueError — exponents can only be raised, by
+        ct^(2^delta)), then ciphertext g is prod_j ct_(g slots + j)^(2^(slot_bits j)) mod n^2 (pai_ct_pack).  `value_bits` is
+        the CALLER'S PROMISE that every mantissa at that exponent satisfies |m| < 2^value_bits: it cannot be checked on
+        ciphertexts, and a broken promise corrupts the neighbouring slots silently (or shows as an OverflowError at
+        decryption).  The result is the canonical residue, not re-randomised (as sum() / segment_sum())."""
+        from . import packed as _packed
+
+        return _packed.pack_encrypted(self, slot_bits=slot_bits, value_bits=value_bits, exponent=exponent, slots=slots)
 
     def csr_rmatmul(self, indptr, indices, data, shape) -> "PaillierEncryptedNumber":
         """Extension: A @ self for a plaintext sparse A given as CSR arrays (numpy, or torch on any device; no scipy needed) of
