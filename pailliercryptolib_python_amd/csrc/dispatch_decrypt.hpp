@@ -461,6 +461,7 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
                 Q.ct_words = pk->ct_words;
                 Q.u_words = sk->u_words;
                 Q.sqr_kara = !knob_disabled("padic_kara");      // PAI_DISABLE=padic_kara: the row-wise squaring
+                Q.mul_kara = !knob_disabled("padic_kara_mul");  // PAI_DISABLE=padic_kara_mul: row-wise products, LDS hand-over
                 if (!launch_dec_a_padic(sk->padic_nl, s, gridx, Q, d_ct, sk->ubuf.as<uint32_t>(), (int)N, sk->table.as<uint32_t>()))
                     throw PaiError(PAI_E_INTERNAL, "no p-adic kernel for this limb count");
             } else if (sk->wide_nl) {

@@ -20,6 +20,7 @@ struct DecPadicParams {
     uint4* wscratch;             // PADIC_WBUF: [NC][nslots] quotient digits of the digit-form entry and the exit
     int ct_words, u_words;
     int sqr_kara;                // 36-limb primes: squarings by sqr_kara (MODE PADIC_LDS_K) instead of the row-wise sqr
+    int mul_kara;                // ... and the products too, digits kept in registers between operations (MODE PADIC_LDS_KM)
 };
 
 // (A, B) <- Montgomery digit form of the packed integer `row` (row_words 32-bit words, any value < s^2 R-ish):
@@ -98,7 +99,11 @@ constexpr int PADIC_XLDS_FROM = 56;          // LDS-qualified digit accesses fro
 constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 // MODE PADIC_LDS_K: PADIC_LDS_M with the squarings in registers (mont_padic.hpp: sqr_kara, signed Karatsuba product columns,
 //                   NL even); the products keep the row-wise form and its LDS quotient-digit buffer.
-constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2;
+// MODE PADIC_LDS_KM: PADIC_LDS_K with the products by Karatsuba columns as well (mul_kara_reg) and the digit pair held in
+//                   registers from the table build to the end of the schedule: a squaring or a product takes its operand
+//                   from the registers the previous one left it in, the right operand of a product is loaded once from the
+//                   table.  LDS serves the row-wise entry (padic_to_digit_form) and exit, which keep the quotient buffer.
+constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3;
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict__ u_out, int n,
@@ -132,6 +137,7 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
     const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * BLOCK_THREADS + threadIdx.x;
     // M: quotient digits of the first half of the product rule: an LDS digit buffer, or (PADIC_WBUF) a strided global column
     const typename E::MBuf M = MODE == PADIC_WBUF ? typename E::MBuf{P.wscratch + slot, nslots} : typename E::MBuf{B + E::NC * 64, 64};
+    // SQR / MUL / SQRN serve the LDS-resident modes only; PADIC_LDS_KM calls sqr_kara_reg / mul_kara_reg on registers below
     auto SQR = [&]() {
         if constexpr (MODE == PADIC_WBUF) {
             if constexpr (NL <= PADIC_SQR_SYM_MAX_NL) E::sqr_sym_fused(A, B, nm, pm1, n0inv);
@@ -157,47 +163,100 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         const uint32_t* row = ct + (size_t)es * P.ct_words;
         // ---- digit form of ct:  sum_i  (c_i, 0) * digits(R^(i+2) mod s^2) -----------------------------
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
-        // ---- table of odd powers: T[i] = base^(2i+1); slot `tbl_entries` keeps base^2 -----------------------
-        const int NT = P.tbl_entries;
-#pragma unroll 1
-        for (int c = 0; c < E::NC; ++c) { tbl(0, 0, c) = E::ld(A, c); tbl(0, 1, c) = E::ld(B, c); }
-        auto from_table = [&](int e, int d) {
-            return [&, e, d](int blk, uint32_t (&xv)[U]) {
+        if constexpr (MODE == PADIC_LDS_KM) {
+            // ---- table of odd powers and sliding-window schedule on register digits ----------------------------------
+            // ONE loop and so one inlined copy of the squaring and of the product (each is tens of KB of straight-line
+            // code): step 0 squares the base (-> slot NT), steps 1 .. NT-1 multiply by base^2 (-> slots 1 .. NT-1), then
+            // the schedule entries 1 .. nops-1 follow.
+            //   t            squarings   product by       then put (a, b) to   then get (a, b) from
+            //   0            1           -                slot NT (base^2)     slot 0 (slot i0 if NT == 1)
+            //   1 .. NT-1    0           slot NT          slot t               - (slot i0 after t == NT-1)
+            //   NT ..        ops: nsq    ops: idx | none  -                    -
+            // idx == 0xFF is the schedule's "no product"; step 0 borrows it, table indices stay below it.
+            static_assert(PADIC_TBL_ENTRIES < 0xFF, "0xFF marks a step without product");
+            const int NT = P.tbl_entries;
+            uint32_t a[NL], b[NL];
+            E::load_digit(A, a);
+            E::load_digit(B, b);
+            auto put = [&](int e) {
 #pragma unroll
-                for (int c = 0; c < E::UC; ++c) {
-                    const uint4 t = tbl(e, d, E::UC * blk + c);
-                    xv[4 * c] = t.x; xv[4 * c + 1] = t.y; xv[4 * c + 2] = t.z; xv[4 * c + 3] = t.w;
+                for (int c = 0; c < E::NC; ++c) {
+                    tbl(e, 0, c) = make_uint4(a[4 * c], a[4 * c + 1], a[4 * c + 2], a[4 * c + 3]);
+                    tbl(e, 1, c) = make_uint4(b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3]);
                 }
             };
-        };
-        SQRN(1);
-#pragma unroll 1
-        for (int c = 0; c < E::NC; ++c) { tbl(NT, 0, c) = E::ld(A, c); tbl(NT, 1, c) = E::ld(B, c); }
-        wave_lds_fence();
-#pragma unroll 1
-        for (int c = 0; c < E::NC; ++c) { E::st(A, c, tbl(0, 0, c)); E::st(B, c, tbl(0, 1, c)); }
-        wave_lds_fence();
-#pragma unroll 1
-        for (int k = 1; k < NT; ++k) {
-            MUL(from_table(NT, 0), from_table(NT, 1));
-#pragma unroll 1
-            for (int c = 0; c < E::NC; ++c) { tbl(k, 0, c) = E::ld(A, c); tbl(k, 1, c) = E::ld(B, c); }
-        }
-        // ---- sliding-window schedule (wave-uniform, compiled on the host from s - 1) --------------------
-        {
+            put(0);
             const int i0 = (int)(ops[0] >> 8);
+            const int steps = NT + nops - 1;
+#pragma unroll 1
+            for (int t = 0; t < steps; ++t) {
+                int nsq = 0, idx = NT, put_e = t, get_e = -1;
+                if (t == 0) { nsq = 1; idx = 0xFF; put_e = NT; get_e = 0; }
+                else if (t >= NT) {
+                    const int op = (int)ops[t - NT + 1];
+                    nsq = op & 0xFF; idx = op >> 8; put_e = -1;
+                }
+                if (t == NT - 1) get_e = i0;             // the table is complete: start from the first window's entry
+#pragma unroll 1
+                for (int s = 0; s < nsq; ++s) E::sqr_kara_reg(a, b, nm, n0inv);
+                if (idx != 0xFF) E::mul_kara_reg(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nm, n0inv);
+                if (put_e >= 0) put(put_e);
+                if (get_e >= 0) {
+#pragma unroll
+                    for (int c = 0; c < E::NC; ++c) {
+                        const uint4 ta = tbl(get_e, 0, c), tb = tbl(get_e, 1, c);
+                        a[4 * c] = ta.x; a[4 * c + 1] = ta.y; a[4 * c + 2] = ta.z; a[4 * c + 3] = ta.w;
+                        b[4 * c] = tb.x; b[4 * c + 1] = tb.y; b[4 * c + 2] = tb.z; b[4 * c + 3] = tb.w;
+                    }
+                }
+            }
+            wave_lds_fence();
+            E::store_digit(A, a);
+            E::store_digit(B, b);
+            wave_lds_fence();
+        } else {
+            // ---- table of odd powers: T[i] = base^(2i+1); slot `tbl_entries` keeps base^2 -----------------------
+            const int NT = P.tbl_entries;
+#pragma unroll 1
+            for (int c = 0; c < E::NC; ++c) { tbl(0, 0, c) = E::ld(A, c); tbl(0, 1, c) = E::ld(B, c); }
+            auto from_table = [&](int e, int d) {
+                return [&, e, d](int blk, uint32_t (&xv)[U]) {
+#pragma unroll
+                    for (int c = 0; c < E::UC; ++c) {
+                        const uint4 t = tbl(e, d, E::UC * blk + c);
+                        xv[4 * c] = t.x; xv[4 * c + 1] = t.y; xv[4 * c + 2] = t.z; xv[4 * c + 3] = t.w;
+                    }
+                };
+            };
+            SQRN(1);
+#pragma unroll 1
+            for (int c = 0; c < E::NC; ++c) { tbl(NT, 0, c) = E::ld(A, c); tbl(NT, 1, c) = E::ld(B, c); }
             wave_lds_fence();
 #pragma unroll 1
-            for (int c = 0; c < E::NC; ++c) { E::st(A, c, tbl(i0, 0, c)); E::st(B, c, tbl(i0, 1, c)); }
+            for (int c = 0; c < E::NC; ++c) { E::st(A, c, tbl(0, 0, c)); E::st(B, c, tbl(0, 1, c)); }
             wave_lds_fence();
-        }
 #pragma unroll 1
-        for (int k = 1; k < nops; ++k) {
-            const int op = (int)ops[k];
-            const int nsq = op & 0xFF, idx = op >> 8;
-            SQRN(nsq);
-            if (idx != 0xFF) {
-                MUL(from_table(idx, 0), from_table(idx, 1));
+            for (int k = 1; k < NT; ++k) {
+                MUL(from_table(NT, 0), from_table(NT, 1));
+#pragma unroll 1
+                for (int c = 0; c < E::NC; ++c) { tbl(k, 0, c) = E::ld(A, c); tbl(k, 1, c) = E::ld(B, c); }
+            }
+            // ---- sliding-window schedule (wave-uniform, compiled on the host from s - 1) --------------------
+            {
+                const int i0 = (int)(ops[0] >> 8);
+                wave_lds_fence();
+#pragma unroll 1
+                for (int c = 0; c < E::NC; ++c) { E::st(A, c, tbl(i0, 0, c)); E::st(B, c, tbl(i0, 1, c)); }
+                wave_lds_fence();
+            }
+#pragma unroll 1
+            for (int k = 1; k < nops; ++k) {
+                const int op = (int)ops[k];
+                const int nsq = op & 0xFF, idx = op >> 8;
+                SQRN(nsq);
+                if (idx != 0xFF) {
+                    MUL(from_table(idx, 0), from_table(idx, 1));
+                }
             }
         }
         // ---- leave Montgomery form: multiply by the plain element 1 = (1, 0) ----------------------------

@@ -698,35 +698,57 @@ struct Padic {
     // the product column goes through a carry stream of its own (cc) and only its low 29 bits, doubled for 2 a b, enter
     // the reduction column with the quotient products, so neither 64-bit sum can wrap:  cc <= 2^63.2 + 2^35 and
     // d <= NL 2^58 + 2^36 + 2^30.
-    // SECOND = false: w = (a^2 + m p) / R, quotient digits to mq.
-    // SECOND = true:  v = (2 a b - min + R p + m' p) / R  (R p - m = (R - 1 - m) + 1 + (p - 1) R; p - 1 = p with limb 0 less).
-    // w and v equal those of the row-wise sqr() exactly (the quotient digits are unique modulo R).
-    template <bool SECOND>
+    // FORM (compile time):
+    //   KARA_SQR   w = (x^2 + m p) / R, quotient digits to mq (y = x; pairs i < l doubled, the diagonal once).
+    //   KARA_SQR2  v = (2 x y - min + R p + m' p) / R: the low 29 bits of the product stream enter doubled.
+    //   KARA_MUL   w = (x y + m p) / R with x != y, not doubled, quotient digits to mq.
+    //   KARA_MUL2  v = (x y + x2 y2 - min + R p + m' p) / R, the SUM of two products (a d + b c of the product rule).
+    // (R p - min = (R - 1 - min) + 1 + (p - 1) R; p - 1 = p with limb 0 less.)
+    // Cells of KARA_MUL2.  One product column is < NL 2^58 < 2^64, the sum of two is up to 2 NL 2^58 > 2^64, so the sum never
+    // sits in one 64-bit cell.  The half products of the two pairs ARE summed, P0 = x0 y0 + x2_0 y2_0 and likewise P2: a
+    // coefficient has at most H products per pair, 2 H 2^58 = NL 2^58 < 2^64, and only one set of 2 x H of them is live, as
+    // for a single product.  The outer part of column k (P0_k, or P2_(k-2H): never both) goes through the carry stream cc
+    // first and leaves 29 bits; the middle part P0_j + P2_j - D_j, j = k - H (the x0 y1 + x1 y0 terms of both pairs, up to
+    // 4 H = 2 NL products) is then added to those 29 bits in a 128-bit cell: P0_j, P2_j < 2^63.2 unsigned, -D_j of EITHER pair
+    // a sum of H signed products, |.| < 2^62.2, exact in int64 at every partial sum (the two together can pass 2^63, so each
+    // has its own cell and is sign-extended into the wide one); the cell is in [0, 2 NL 2^58 + 2^29) = [0, 2^64.2) and its carry joins cc:
+    // cc < 2^34.2 + 2^35.2 < 2^35.8, outer + cc < 2^63.3.  The reduction column is d <= NL 2^58 + 2^30 + 2^36 as before.
+    // w and v equal those of the row-wise sqr() / mul() exactly (the quotient digits are unique modulo R).  The difference
+    // limbs depend on one operand each: after inlining, the two passes of one product share those of the left digit a and of
+    // the right digit c (common subexpressions), so each is formed once per product.
+    static constexpr int KARA_SQR = 0, KARA_SQR2 = 1, KARA_MUL = 2, KARA_MUL2 = 3;
+    template <int FORM>
     PAI_DEV static void kara_pass(uint32_t (&out)[NL], uint32_t (&mq)[NL], const uint32_t (&x)[NL], const uint32_t (&y)[NL],
-                                  const uint32_t (&min)[NL], const uint32_t* __restrict__ nm, uint32_t n0inv) {
+                                  const uint32_t (&x2)[NL], const uint32_t (&y2)[NL], const uint32_t (&min)[NL],
+                                  const uint32_t* __restrict__ nm, uint32_t n0inv) {
         static_assert(NL % 2 == 0, "even limb count");
+        constexpr bool SYM = FORM == KARA_SQR, DBL = FORM == KARA_SQR2, SUM = FORM == KARA_MUL2;
+        constexpr bool SECOND = DBL || SUM;               // - min + R p enters the reduction columns
         constexpr int H = NL / 2, NP = 2 * H - 1;         // half-product coefficients 0 .. NP - 1
         int32_t nx[H], dy[H];                             // nx = x1 - x0, dy = y0 - y1: nx * dy = -(x0 - x1)(y0 - y1)
-        uint32_t y2[NL];                                  // doubled limbs for the symmetric square
-        int32_t dy2[H];
+        int32_t nx2[H], dy2[H];                           // SUM: the same for the second pair; SYM: dy doubled
+        uint32_t yd[NL];                                  // doubled limbs for the symmetric square
 #pragma unroll
         for (int i = 0; i < H; ++i) {
             nx[i] = (int32_t)x[i + H] - (int32_t)x[i];
             dy[i] = (int32_t)y[i] - (int32_t)y[i + H];
-            dy2[i] = dy[i] * 2;
+            nx2[i] = SUM ? (int32_t)x2[i + H] - (int32_t)x2[i] : 0;
+            dy2[i] = SUM ? (int32_t)y2[i] - (int32_t)y2[i + H] : dy[i] * 2;
         }
 #pragma unroll
-        for (int i = 0; i < NL; ++i) y2[i] = y[i] << 1;
-        // half product of limbs [o, o + H) of x and y, coefficient j (a square: pairs i < l doubled, the diagonal once)
+        for (int i = 0; i < NL; ++i) yd[i] = y[i] << 1;
+        // half product of limbs [o, o + H) of x and y, coefficient j (a square: pairs i < l doubled, the diagonal once;
+        // SUM: both pairs)
         auto half = [&](int o, int j) -> uint64_t {
             uint64_t s = 0;
             const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
 #pragma unroll
             for (int i = lo; i <= hi; ++i) {
                 const int l = j - i;
-                if (SECOND) s += (uint64_t)x[o + i] * y[o + l];
-                else if (i < l) s += (uint64_t)x[o + i] * y2[o + l];
+                if (!SYM) s += (uint64_t)x[o + i] * y[o + l];
+                else if (i < l) s += (uint64_t)x[o + i] * yd[o + l];
                 else if (i == l) s += (uint64_t)x[o + i] * y[o + i];
+                if (SUM) s += (uint64_t)x2[o + i] * y2[o + l];
             }
             return s;
         };
@@ -735,24 +757,32 @@ struct Padic {
 #pragma unroll
         for (int k = 0; k < 2 * NL - 1; ++k) {
             uint64_t t = 0;
+            int64_t nd = 0, nd2 = 0;                      // SUM: -D_j of either pair
             if (k < NP) { p0[k] = half(0, k); t += p0[k]; }
             if (k >= H && k - H < NP) {
                 const int j = k - H;
                 p2[j] = half(H, j);
-                t += p0[j] + p2[j];
+                if (!SUM) t += p0[j] + p2[j];
                 const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
 #pragma unroll
                 for (int i = lo; i <= hi; ++i) {
                     const int l = j - i;
-                    if (SECOND) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
+                    if (SUM) { nd += (int64_t)nx[i] * (int64_t)dy[l]; nd2 += (int64_t)nx2[i] * (int64_t)dy2[l]; }
+                    else if (!SYM) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
                     else if (i < l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy2[l]);
                     else if (i == l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[i]);
                 }
             }
             if (k >= 2 * H) t += p2[k - 2 * H];
-            const uint64_t c = t + cc;
+            uint64_t c = t + cc;
             cc = c >> RB;
-            const uint64_t lowc = SECOND ? (uint64_t)(((uint32_t)c & RMASK) << 1) : (uint64_t)((uint32_t)c & RMASK);
+            if (SUM && k >= H && k - H < NP) {
+                const unsigned __int128 e = (unsigned __int128)p0[k - H] + p2[k - H] + (unsigned __int128)(__int128)nd +
+                                           (unsigned __int128)(__int128)nd2 + ((uint32_t)c & RMASK);
+                cc += (uint64_t)(e >> RB);
+                c = (uint64_t)e;
+            }
+            const uint64_t lowc = DBL ? (uint64_t)(((uint32_t)c & RMASK) << 1) : (uint64_t)((uint32_t)c & RMASK);
             uint64_t d = lowc;
             if (SECOND) d += k < NL ? (uint64_t)((RMASK - min[k]) + (k == 0 ? 1u : 0u)) : (uint64_t)(nm[k - NL] - (k == NL ? 1u : 0u));
             const int lo = k < NL ? 0 : k - NL + 1, hi = k < NL ? k - 1 : NL - 1;
@@ -770,7 +800,7 @@ struct Padic {
             }
             carry = d >> RB;
         }
-        out[NL - 1] = (uint32_t)(carry + (SECOND ? (cc << 1) + nm[NL - 1] : cc)) & RMASK;
+        out[NL - 1] = (uint32_t)(carry + (DBL ? cc << 1 : cc) + (SECOND ? nm[NL - 1] : 0u)) & RMASK;
     }
     PAI_DEV static void load_digit(const uint4* x, uint32_t (&r)[NL]) {
 #pragma unroll
@@ -782,16 +812,47 @@ struct Padic {
     PAI_DEV static void sqr_kara(uint4* A, uint4* B, const uint32_t* __restrict__ nm, uint32_t n0inv) {
         uint32_t a[NL], m[NL], w[NL];
         load_digit(A, a);
-        kara_pass<false>(w, m, a, a, m, nm, n0inv);
+        kara_pass<KARA_SQR>(w, m, a, a, a, a, m, nm, n0inv);
         // a stays in registers for the second pass: w can take its place in LDS now
         wave_lds_fence();
         store_digit(A, w);
         uint32_t b[NL], m2[NL], v[NL];
         load_digit(B, b);
-        kara_pass<true>(v, m2, a, b, m, nm, n0inv);
+        kara_pass<KARA_SQR2>(v, m2, a, b, a, b, m, nm, n0inv);
         wave_lds_fence();
         store_digit(B, v);
         wave_lds_fence();
+    }
+    // ---- the same on digits that STAY in registers from one operation to the next (kernels_padic.hpp: PADIC_LDS_KM) -----
+    // (a, b) <- (a, b)^2
+    PAI_DEV static void sqr_kara_reg(uint32_t (&a)[NL], uint32_t (&b)[NL], const uint32_t* __restrict__ nm, uint32_t n0inv) {
+        uint32_t m[NL], w[NL], m2[NL], v[NL];
+        kara_pass<KARA_SQR>(w, m, a, a, a, a, m, nm, n0inv);
+        kara_pass<KARA_SQR2>(v, m2, a, b, a, b, m, nm, n0inv);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
+    }
+    // (a, b) <- (a, b) * (c, d): w = (a c + m p) / R, v = (a d + b c - m + R p + m' p) / R, 3 H^2 + 6 H^2 + 2 NL^2 limb
+    // products (5 508 at 36 limbs) instead of the row-wise 5 NL^2 (6 480).  rsrc(g, ch): chunk ch of the right operand's
+    // digit g (0 = c, 1 = d), each chunk loaded once; d is fetched behind the first pass.
+    template <class RSrc>
+    PAI_DEV static void mul_kara_reg(uint32_t (&a)[NL], uint32_t (&b)[NL], RSrc&& rsrc, const uint32_t* __restrict__ nm,
+                                     uint32_t n0inv) {
+        uint32_t c[NL], d[NL], m[NL], w[NL], m2[NL], v[NL];
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            const uint4 t = rsrc(0, ch);
+            c[4 * ch] = t.x; c[4 * ch + 1] = t.y; c[4 * ch + 2] = t.z; c[4 * ch + 3] = t.w;
+        }
+        kara_pass<KARA_MUL>(w, m, a, c, a, c, m, nm, n0inv);
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            const uint4 t = rsrc(1, ch);
+            d[4 * ch] = t.x; d[4 * ch + 1] = t.y; d[4 * ch + 2] = t.z; d[4 * ch + 3] = t.w;
+        }
+        kara_pass<KARA_MUL2>(v, m2, a, d, b, c, m, nm, n0inv);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }
 
     // (A, B) <- (A, B) * (C, D), the second operand's digits supplied per row block

@@ -31,7 +31,8 @@ bool launch_dec_a_padic(int nl, hipStream_t s, int gridx, const DecPadicParams& 
     switch (nl) {
         case 24: launch_padic<24, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table); return true;
         case 36:
-            if (P.sqr_kara) launch_padic<36, 12, PADIC_LDS_K>(s, gridx, P, ct, u_out, n, table);
+            if (P.sqr_kara && P.mul_kara) launch_padic<36, 12, PADIC_LDS_KM>(s, gridx, P, ct, u_out, n, table);
+            else if (P.sqr_kara) launch_padic<36, 12, PADIC_LDS_K>(s, gridx, P, ct, u_out, n, table);
             else launch_padic<36, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table);
             return true;
         case 56: launch_padic<56, 8, PADIC_WBUF>(s, gridx, P, ct, u_out, n, table); return true;
