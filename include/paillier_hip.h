@@ -260,6 +260,22 @@ int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
 int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, const uint32_t* d_rows, const int32_t* d_shift,
                         const int64_t* d_offsets, size_t S, uint32_t* d_out, void* stream);
 
+/* Segment scans behind PaillierEncryptedNumber.cumsum (extension; no reference counterpart): the N rows of d_ct are N / seg_len
+ * contiguous runs of seg_len rows, and within each run, in scan order (ascending rows, or descending when reverse != 0),
+ *     acc_first = ct_first^(2^raise_first),   acc_i = acc_prev^(2^step_i) * ct_i^(2^raise_i)  mod n^2,
+ *     d_out[i] = acc_i * R^dom_out, the canonical residue (dom_out = 0: the wire form).
+ * With raise_i = E_i - e_i and step_i = E_i - E_(i-1), E the running maximum of the exponents e, row i is the exponent-aligned sum
+ * of its run's rows up to i.  d_ct: [N][ct_words] at domain tag `tag` (pai_ct_mont_mul; |tag|, |dom_out| <= 46); d_raise, d_step:
+ * int32 [N] indexed by row, NULL = all 0; the step of a run's first row is ignored; both may be non-zero on one row.  seg_len must
+ * divide N (PAI_E_INVALID otherwise); d_out: [N][ct_words], must not alias d_ct.  A negative raise or step counts as 0 and sets
+ * bit 4 of the handle's status word (pai_pubkey_status).  Cost: 1 + [tag != 1] + [dom_out != 1] Montgomery products per row plus
+ * one per squaring, when there are enough runs to give every lane group of the device one.  Fewer runs are cut into chunks
+ * (PAI_TUNE scan_chunk: the chunk length): chunk totals, the scan of the totals (the same call on the handle's scratch, level by
+ * level), then the chunks again, seeded with their carries — three launches and about twice the products per level, and no
+ * workgroup waits for another.  Runs are uniform, so no size is read back: the call is fully asynchronous on `stream`. */
+int pai_ct_scan(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int dom_out, size_t seg_len, int reverse,
+                const int32_t* d_raise, const int32_t* d_step, uint32_t* d_out, void* stream);
+
 /* Sparse multi-exponentiation behind PaillierEncryptedNumber.csr_matmul / csr_rmatmul and the scipy forms of @ (extension; no
  * reference counterpart): T terms in segment order, d_out[s] = prod over the terms t = d_offsets[s] .. d_offsets[s+1] - 1 of
  * B_t^(e_t) mod n^2, in the wire form (canonical residues); an empty segment gives 1.  B_t = d_ct[d_base[t]], or
@@ -292,7 +308,7 @@ int pai_ct_pow2_hint(const pai_pubkey* pk, uint32_t* d_ct, const int32_t* d_delt
  * then wrong — a hint outside that range runs the lane-group kernel, which is correct for any shift, and flags nothing); bit 2 —
  * a pai_ct_segment_prod call met a member row >= N (skipped) or a negative shift (taken as 0); bit 3 — a pai_ct_sparse_multiexp
  * call met a base outside [0, N) (the term skipped) or segment offsets that step back or leave [0, T] (clamped; the terms they
- * drop are skipped).  The Python layer computes its hints from host arrays, uses pai_ct_invert_flag and builds and checks its
+ * drop are skipped); bit 4 — a pai_ct_scan call met a negative raise or step (taken as 0).  The Python layer computes its hints from host arrays, uses pai_ct_invert_flag and builds and checks its
  * segment and term plans itself, so it never depends on this word. */
 int pai_pubkey_status(const pai_pubkey* pk, int* status_out, int clear, void* stream);
 

@@ -78,6 +78,7 @@ PROTOTYPES = {
     "pai_ct_multiexp": (C.c_int, [voidp, voidp, voidp, C.c_size_t, C.c_size_t, C.c_size_t, voidp, C.c_int, C.c_int, voidp, voidp,
                                   voidp]),
     "pai_ct_segment_prod": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
+    "pai_ct_scan": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_int, voidp, voidp, voidp, voidp]),
     "pai_ct_sparse_multiexp": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp, C.c_int, C.c_int, voidp, C.c_size_t, voidp,
                                          C.c_size_t, voidp, voidp]),
     "pai_shard_plan": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -192,6 +192,12 @@ struct GeoInst {
         report_occupancy("k_segprod", (const void*)k_segprod<GM>, bytes);
         hipLaunchKernelGGL(k_segprod<GM>, dim3(grid), dim3(BLOCK_THREADS), bytes, s, c, A, w32, rpow);
     }
+    static void segscan(hipStream_t s, int grid, const MontCtx* c, ScanArgs A, int w32, const uint32_t* rpow) {
+        constexpr int bytes = GM::LDS_BYTES + GM::STAGE_BYTES;
+        set_lds((const void*)k_segscan<GM>, bytes);
+        report_occupancy("k_segscan", (const void*)k_segscan<GM>, bytes);
+        hipLaunchKernelGGL(k_segscan<GM>, dim3(grid), dim3(BLOCK_THREADS), bytes, s, c, A, w32, rpow);
+    }
     static void mexp_table(hipStream_t s, int grid, const MontCtx* c, const uint32_t* ct, const uint32_t* ct_inv, int w32,
                            uint32_t* table, int nentries, int nsigns, int wbits) {
         set_lds((const void*)k_mexp_table<G>, G::LDS_BYTES);
@@ -223,7 +229,7 @@ struct GeoInst {
     static const GeoOps* ops() {
         static const GeoOps o = {G::NLL, G::T, G::U, G::NL, G::EPB, G::LDS_BYTES, 2 * G::LDS_WORDS * 4,
                                  &modmul, &modexp_fixed, &modexp_var, &modexp_var_win, &encrypt, &fb_expand, &dec_a, &dec_b, &pow2, &sq_chain, &add_aligned, &addn, &table_words, &pair_finish, &mexp_table, &mexp,
-                                 G::T <= 8 ? &modmul_msb : nullptr, &segprod, &smexp};
+                                 G::T <= 8 ? &modmul_msb : nullptr, &segprod, &segscan, &smexp};
         return &o;
     }
 };

@@ -57,6 +57,8 @@ struct GeoOps {
     void (*modmul_msb)(hipStream_t, int grid, const MsbCtx*, const uint32_t* a, const uint32_t* b, uint32_t* out, int n, int w32);
     // segment products (k_segprod): one Horner chain of gathered rows per output; rpow as for addn
     void (*segprod)(hipStream_t, int grid, const MontCtx*, SegArgs, int w32, const uint32_t* rpow);
+    // segment scans (k_segscan): the prefix products of uniform runs, one chain per run or chunk; rpow as for addn
+    void (*segscan)(hipStream_t, int grid, const MontCtx*, ScanArgs, int w32, const uint32_t* rpow);
     // sparse multi-exponentiation (k_smexp): chunks of a term list over the tables of mexp_table, one partial per chunk
     void (*smexp)(hipStream_t, int grid, const MontCtx*, MexpParams, SmexpArgs, const uint32_t* table, const uint32_t* e,
                   const uint8_t* sign, uint32_t* out, int nlanes);

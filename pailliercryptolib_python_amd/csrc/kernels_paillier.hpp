@@ -1293,4 +1293,218 @@ k_segprod(const MontCtx* __restrict__ ctx, SegArgs A, int w32, const uint32_t* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Segment scans (PaillierEncryptedNumber.cumsum, extension): the prefix products of uniform runs of seg_len rows,
+//     acc_first = ct_first^(2^raise_first),   acc_i = acc_prev^(2^step_i) * ct_i^(2^raise_i),   out[i] = acc_i R^dom_out,
+// one chain per lane group with the wave-uniform "one product per iteration" loop of k_segprod — but a row is stored after
+// EVERY member.  A run is cut into chunks of `chunk` scan positions (cpr chunks per run); chain ch = run * cpr + k walks the
+// positions k chunk .. min(seg_len, (k + 1) chunk) - 1 of its run, position p being row run seg_len + p, or, reversed,
+// run seg_len + seg_len - 1 - p (an index map: nothing is copied).
+//
+// Montgomery bookkeeping: everything is closed at tag 1 — montmul(acc R, ct R) = acc ct R, and the square of a tag-1 value
+// has tag 1 — so the accumulator never needs the lazy R^c of k_segprod.  A member at another tag is multiplied by R^(2 - tag)
+// as it is loaded, an output at another dom_out is a copy of the accumulator times R^dom_out: 1 + [tag != 1] + [dom_out != 1]
+// products per element, plus one per squaring.  Every stored row passes cond_sub: canonical.
+//
+// Three uses, by arguments: prefixes of unseeded chains (seed == NULL or the first chunk of a run); prefixes of chains that
+// start from a carry row at tag 1 (seed[ch - 1]: the prefix up to the end of the previous chunk, to which the first member's
+// step applies like any other's); and totals != 0: only the chain's last value, at tag 1, into out[ch], with the sum of the
+// chunk's steps into step_sum[ch] (the first member's included unless it starts a run: the step from the previous chunk's end,
+// which the next level applies to the carry).  A negative raise or step counts as 0 and sets bit 4 of *status.
+struct ScanArgs {
+    const uint32_t* ct;              // [n][w32] rows at R^tag
+    const int32_t* raise;            // [n] squarings of each member, or NULL: all 0
+    const int32_t* step;             // [n] squarings of the accumulator before each member, or NULL: all 0
+    const uint32_t* seed;            // NULL, or [chains][w32] at tag 1
+    uint32_t* out;                   // prefixes: [n][w32] at R^dom_out; totals: [chains][w32] at tag 1
+    int32_t* step_sum;               // totals: NULL or [chains]
+    int* status;
+    int n, tag, dom_out, seg_len, chunk, cpr, chains, reverse, totals;
+};
+
+// The inverse of gather_tile: this wave's staged rows to the packed rows `row` (per lane, the lane group's; < 0: not stored).
+template <class G>
+PAI_DEV void scatter_tile(const uint32_t* stage, uint32_t* __restrict__ dst, int row, int W32) {
+    using WT = WaveTile<G>;
+    const uint32_t* src = WT::slice(const_cast<uint32_t*>(stage));
+    const int lane = WT::lane();
+    wave_lds_fence();
+    if ((W32 & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+        const int wv = W32 >> 2;
+        const int total = WT::EPW * wv;
+        const uint32_t inv = (65536u + (uint32_t)wv - 1u) / (uint32_t)wv;     // c / wv == (c * inv) >> 16 for c < 1024
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
+        uint4 v[WT::IT4];
+        int re[WT::IT4], ke[WT::IT4];
+#pragma unroll
+        for (int it = 0; it < WT::IT4; ++it) {               // every LDS read first, then the stores
+            const int c = lane + it * 64;
+            const int cc = c < total ? c : total - 1;
+            const int e = (int)(((uint32_t)cc * inv) >> 16), k = cc - e * wv;
+            const int r = __shfl(row, e * G::T, 64);
+            re[it] = c < total ? r : -1;
+            ke[it] = k;
+            v[it] = s4[e * WT::SV + k];
+        }
+#pragma unroll
+        for (int it = 0; it < WT::IT4; ++it)
+            if (re[it] >= 0) d4[(size_t)re[it] * wv + ke[it]] = v[it];
+    } else {                                                 // odd word counts / unaligned rows (wave-uniform trip count: the shuffle)
+        constexpr int TOT = WT::EPW * G::SW;
+        for (int b = 0; b < TOT; b += 64) {
+            const int i = b + lane, ic = i < TOT ? i : TOT - 1;
+            const int e = ic / G::SW, k = ic - e * G::SW;
+            const int r = __shfl(row, e * G::T, 64);
+            if (i < TOT && k < W32 && r >= 0) dst[(size_t)r * W32 + k] = src[ic];
+        }
+    }
+    wave_lds_fence();
+}
+
+template <class G>
+__global__ void __launch_bounds__(BLOCK_THREADS, 2)
+k_segscan(const MontCtx* __restrict__ ctx, ScanArgs A, int w32, const uint32_t* __restrict__ rpow) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    using WT = WaveTile<G>;
+    uint32_t* stage = lds + G::LDS_WORDS + G::NL;
+    typename G::NM nm;
+    load_modulus<G>(nm, ctx, lds);
+    const uint32_t n0inv = ctx->n0inv;
+    constexpr int WPB = BLOCK_THREADS / 64;
+    // the first two take no product; OP_CONV and OP_SQ_MEM work on the member, the others on the accumulator
+    enum { OP_NONE = 0, OP_FIRST, OP_MEMBER, OP_SQ_ACC, OP_SQ_MEM, OP_CONV, OP_OUT };
+    const int wtiles = (A.chains + WT::EPW - 1) / WT::EPW;
+    clear_stage<G>(stage);
+    const uint32_t* o_lds = lds + G::elem();             // column of this element in the [limb][element] operand buffer
+    const uint32_t* c_in = rpow + (size_t)(RPOW_SPAN + 2 - A.tag) * G::NL + G::NLL * G::gl();       // member R^tag -> R^1
+    const uint32_t* c_out = rpow + (size_t)(RPOW_SPAN + A.dom_out) * G::NL + G::NLL * G::gl();      // acc R^1 -> R^dom_out
+    const int per_wave = (wtiles + (int)gridDim.x * WPB - 1) / ((int)gridDim.x * WPB);
+    const int wt_begin = ((int)blockIdx.x * WPB + WT::wave()) * per_wave;
+    const int wt_end = min(wtiles, wt_begin + per_wave);
+    for (int wt = wt_begin; wt < wt_end; ++wt) {
+        const int ch = wt * WT::EPW + WT::lane() / G::T; // this lane group's chain
+        const bool live = ch < A.chains;
+        int p = 0, pend = 0, base = 0;                   // scan positions p .. pend - 1 of the run whose rows start at `base`
+        if (live) {
+            const int run = ch / A.cpr, k = ch - run * A.cpr;
+            p = k * A.chunk;
+            pend = min(A.seg_len, p + A.chunk);
+            base = run * A.seg_len;
+        }
+        uint32_t acc[G::NLL], y[G::NLL];
+        set_plain_one<G>(acc);
+        set_plain_one<G>(y);
+        const bool seeded = live && A.seed != nullptr && p > 0;
+        if (__any(seeded)) {                             // the carry: the prefix up to the previous chunk's end, tag 1
+            __builtin_amdgcn_s_setprio(2);
+            gather_tile<G>(stage, A.seed, seeded ? ch - 1 : -1, w32);
+            uint32_t t[G::NLL];
+            unpack_row<G>(t, stage);
+            __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+            for (int i = 0; i < G::NLL; ++i) acc[i] = seeded ? t[i] : acc[i];
+        }
+        int idx = -1;                                    // the current member's row
+        int rz = 0, sq = 0;                              // squarings the member / the accumulator still owe before they meet
+        int ssum = 0;
+        bool has = seeded, done = !live, fetched = false, conv = false, outp = false, bad = false;
+        while (__any(!done)) {                           // wave-uniform: one product per iteration at most
+            int op = OP_NONE;
+            bool fetch = false;
+            if (!done) {
+                if (outp) {
+                    op = OP_OUT;
+                } else if (p < pend) {
+                    if (!fetched) {
+                        idx = base + (A.reverse ? A.seg_len - 1 - p : p);
+                        const int r = A.raise ? A.raise[idx] : 0;
+                        const int s = A.step ? A.step[idx] : 0;
+                        bad |= r < 0 || s < 0;
+                        const int sc = p > 0 && s > 0 ? s : 0;       // the step of a run's first member is ignored
+                        ssum += sc;
+                        sq = has ? sc : 0;
+                        rz = r > 0 ? r : 0;
+                        conv = A.tag != 1;
+                        fetched = fetch = true;
+                    }
+                    op = conv ? OP_CONV : rz > 0 ? OP_SQ_MEM : sq > 0 ? OP_SQ_ACC : has ? OP_MEMBER : OP_FIRST;
+                } else {
+                    done = true;
+                }
+            }
+            if (__any(fetch)) {
+                __builtin_amdgcn_s_setprio(2);
+                gather_tile<G>(stage, A.ct, fetch ? idx : -1, w32);
+                uint32_t t[G::NLL];
+                unpack_row<G>(t, stage);
+                __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) y[i] = fetch ? t[i] : y[i];
+            }
+            const bool on_member = op == OP_CONV || op == OP_SQ_MEM;
+            const bool mul = op >= OP_MEMBER;
+            uint32_t o[G::NLL];                          // the row to store, if this step ends in one
+            if (__any(mul)) {
+                uint32_t lhs[G::NLL], b[G::NLL];
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) {
+                    lhs[i] = on_member ? y[i] : acc[i];
+                    b[i] = op == OP_SQ_ACC ? acc[i] : y[i];
+                }
+                if (__any(op == OP_CONV || op == OP_OUT)) {
+                    const uint32_t* cp = op == OP_OUT ? c_out : c_in;
+#pragma unroll
+                    for (int i = 0; i < G::NLL; ++i) {
+                        const uint32_t v = cp[i];
+                        b[i] = (op == OP_CONV || op == OP_OUT) ? v : b[i];
+                    }
+                }
+                stage_b<G>(b, lds);
+                uint32_t r[G::NLL];
+                mont_mul<G::NLL, G::U, G::T>(r, lhs, o_lds, G::EPB, nm, n0inv);
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) {
+                    y[i] = on_member ? r[i] : y[i];
+                    acc[i] = (op == OP_MEMBER || op == OP_SQ_ACC) ? r[i] : (op == OP_FIRST ? y[i] : acc[i]);
+                    o[i] = op == OP_OUT ? r[i] : acc[i];
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < G::NLL; ++i) {
+                    acc[i] = op == OP_FIRST ? y[i] : acc[i];
+                    o[i] = acc[i];
+                }
+            }
+            int srow = -1;                               // >= 0: this step stores row srow
+            if (op == OP_CONV) conv = false;
+            if (op == OP_SQ_MEM) --rz;
+            if (op == OP_SQ_ACC) --sq;
+            if (op == OP_FIRST || op == OP_MEMBER) {
+                has = true;
+                fetched = false;
+                ++p;
+                if (A.totals) srow = p == pend ? ch : -1;
+                else if (A.dom_out == 1) srow = idx;
+                else outp = true;
+            }
+            if (op == OP_OUT) {
+                outp = false;
+                srow = idx;
+            }
+            if (__any(srow >= 0)) {
+                cond_sub<G::NLL, G::T>(o, nm);
+                __builtin_amdgcn_s_setprio(2);
+                pack_row<G>(o, stage);
+                scatter_tile<G>(stage, A.out, srow, w32);
+                __builtin_amdgcn_s_setprio(0);
+            }
+        }
+        if (G::gl() == 0 && live) {
+            if (A.step_sum) A.step_sum[ch] = ssum;
+            if (bad && A.status) atomicOr(A.status, 16);
+        }
+    }
+}
+
 }  // namespace pai

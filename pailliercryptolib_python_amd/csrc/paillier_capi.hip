@@ -375,7 +375,7 @@ struct ScopedKernelTimer {
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
-//                                  segprod_chunk, smexp_chunk, pack_padic_min
+//                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -522,7 +522,7 @@ struct pai_pubkey {
     // sticky device status word of the asynchronous calls (pai_pubkey_status): bit 0 = pai_ct_invert_async met a
     // ciphertext that is not a unit, bit 1 = a pai_ct_pow2_hint hint was smaller than a shift of its batch, bit 2 =
     // pai_ct_segment_prod met a member row >= N or a negative shift, bit 3 = pai_ct_sparse_multiexp met a base >= N or segment
-    // offsets that step back or leave [0, T]
+    // offsets that step back or leave [0, T], bit 4 = pai_ct_scan met a negative raise or step
     mutable DevBuf status;
     mutable DevBuf prod_a, prod_b;     // ping-pong levels of pai_ct_prod
     // Product trees run on single Montgomery products (k_modmul MODMUL_MONT); level k of a tree holds true values
@@ -1318,6 +1318,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_ctmul.hpp"
 #include "dispatch_add.hpp"
 #include "dispatch_reduce.hpp"
+#include "dispatch_scan.hpp"
 #include "dispatch_pack.hpp"
 #include "dispatch_decrypt.hpp"
 

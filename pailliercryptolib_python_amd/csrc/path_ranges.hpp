@@ -173,6 +173,20 @@ static size_t segprod_chunk(size_t ncu, int epb, size_t members) {
     return std::max<size_t>(4, (members + want - 1) / want);
 }
 
+// ---- segment scans ------------------------------------------------------------------------------------------------------------
+// Chunk length of one level of pai_ct_scan: N rows in runs of seg_len.  With at least one round of resident chains' worth of runs
+// (two workgroups of epb lane groups per CU) a run is one chain: the result is seg_len, "do not chunk".  Otherwise the runs are cut
+// so that the chunks fill that round, at least 4 positions each (a level costs three launches and two products per element; a
+// level of chunks shorter than 4 would not pay for them).  PAI_TUNE scan_chunk overrides (>= 1; tests force 1 / 2 / 3 / 5 and
+// with them several levels; the dispatcher raises it to 2 below the first level, where 1 would never end).
+static size_t scan_chunk(size_t ncu, int epb, size_t N, size_t seg_len) {
+    long long v;
+    if (knob_tune("scan_chunk", &v) && v >= 1) return (size_t)v;
+    const size_t want = std::max<size_t>(1, ncu * (size_t)epb * 2);
+    if (seg_len == 0 || N / seg_len >= want) return seg_len;
+    return std::max<size_t>(4, (N + want - 1) / want);
+}
+
 // ---- sparse multi-exponentiation --------------------------------------------------------------------------------------------------
 // PAI_TUNE smexp_chunk: terms per lane (or lane group) of pai_ct_sparse_multiexp (>= 1; tests force 1 / 2 / 3).  Default: as
 // pai_ct_multiexp, enough chunks to fill `want_lanes` lanes, the rest of the sharing goes into longer chunks (the squarings of a

@@ -403,6 +403,21 @@ class PublicKeyHandle:
                                                    _ptr(out), _stream(self.device)))
         return out
 
+    def ct_scan(self, ct: torch.Tensor, seg_len: int, *, tag: int = 0, dom_out: int = 1, reverse: bool = False,
+                raise_: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The prefix products of the N / seg_len contiguous runs of ct (pai_ct_scan): in scan order (descending rows when
+        reverse), acc_i = acc_prev^(2^step[i]) * ct[i]^(2^raise_[i]) and out[i] = acc_i R^dom_out.  ct: rows at domain tag `tag`;
+        raise_, step: int32 [N] indexed by row (None: all 0; the step of a run's first row is ignored).  Asynchronous."""
+        self._chk(ct, self.ct_words, "ct")
+        n = ct.shape[0]
+        for name, t in (("raise_", raise_), ("step", step)):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"{name}: expected contiguous int32 [N] on {self.device}")
+        out = self.empty_ct(n)
+        _native.check(self.lib.pai_ct_scan(self.h, _ptr(ct), n, int(tag), int(dom_out), int(seg_len), 1 if reverse else 0, _ptr(raise_),
+                                           _ptr(step), _ptr(out), _stream(self.device)))
+        return out
+
     def ct_sparse_multiexp(self, ct: torch.Tensor, ct_inv: Optional[torch.Tensor], base: torch.Tensor, e: torch.Tensor, ebits_max: int,
                            sign: Optional[torch.Tensor], offsets: torch.Tensor) -> torch.Tensor:
         """out[s] = prod over the terms t = offsets[s] .. offsets[s+1]-1 of (ct or, sign[t] != 0, ct_inv)[base[t]]^e[t] mod n^2
@@ -485,6 +500,8 @@ class PublicKeyHandle:
         if v.value & 8:
             raise _native.NativeError(_native.PAI_E_INVALID, "ct_sparse_multiexp: a base was out of range or the offsets were not a "
                                                              "nondecreasing list in [0, T]")
+        if v.value & 16:
+            raise _native.NativeError(_native.PAI_E_INVALID, "ct_scan: a raise or step count was negative")
 
     def ct_pow2_(self, ct: torch.Tensor, delta, max_delta: Optional[int] = None) -> torch.Tensor:
         """ct_i <- ct_i^(2^delta_i) in place for delta_i > 0.  delta: int32 device tensor, or a host numpy array (then the

@@ -483,6 +483,42 @@ def _segment_plan(ids: torch.Tensor, expo: np.ndarray, num_segments: int):
     return row_s.to(torch.int32), shift.to(torch.int32), offsets.contiguous(), seg_expo
 
 
+def _cumsum_args(segment_length, n: int) -> int:
+    """cumsum's argument checks: the run length L for a container of n elements (None: one run of n).  Raises TypeError /
+    ValueError before anything is launched."""
+    if segment_length is None:
+        return n
+    if isinstance(segment_length, (bool, np.bool_)) or not isinstance(segment_length, (int, np.integer)):
+        raise TypeError("cumsum: segment_length must be an integer or None")
+    L = int(segment_length)
+    if L <= 0:
+        raise ValueError("cumsum: segment_length must be positive")
+    if n % L:
+        raise ValueError(f"cumsum: segment_length ({L}) does not divide the number of elements ({n})")
+    return L
+
+
+def _scan_plan(expo, L: int, reverse: bool):
+    """The exponent plan of cumsum on runs of L elements: (raise_, step, out_expo), int32 arrays indexed by element.  Along the
+    scan order of a run (descending elements when reverse) E is the running maximum of the exponents e: out_expo = E,
+    step_i = E_i - E_prev (0 at a run's first element: the squarings of the accumulator before element i joins) and
+    raise_i = E_i - e_i (the squarings of the element); at most one of the two is non-zero.  raise_ and step are None when all
+    exponents are equal (nothing to align)."""
+    e = np.asarray(expo, dtype=np.int64).reshape(-1)
+    if e.size == 0 or bool((e == e[0]).all()):
+        return None, None, e.astype(np.int32)
+    e = e.reshape(-1, L)
+    if reverse:
+        e = e[:, ::-1]
+    E = np.maximum.accumulate(e, axis=1)
+    step = np.zeros_like(E)
+    step[:, 1:] = E[:, 1:] - E[:, :-1]
+    raise_ = E - e
+    if reverse:
+        E, step, raise_ = E[:, ::-1], step[:, ::-1], raise_[:, ::-1]
+    return tuple(np.ascontiguousarray(a).reshape(-1).astype(np.int32) for a in (raise_, step, E))
+
+
 # ---- sparse matrix products (csr_matmul / csr_rmatmul): terms (output element s, base row b, plaintext weight v) -----------------
 # routes taken by the sparse products since import: "fast" = pai_ct_sparse_multiexp, "composite" = gather, * and segment_sum
 SPARSE_ROUTES = {"fast": 0, "composite": 0}
@@ -1114,6 +1150,32 @@ class PaillierEncryptedNumber:
         rows, shift, offsets, seg_expo = _segment_plan(ids.to(h.device), self._expo, int(num_segments))
         out = h.ct_segment_prod(t, rows, shift, offsets, tag=dom)
         return self._wrap(out, seg_expo.cpu().numpy().astype(np.int32), out.shape[0])
+
+    def cumsum(self, segment_length: Optional[int] = None, *, reverse: bool = False) -> "PaillierEncryptedNumber":
+        """Extension: prefix sums.  The N elements are read as N / segment_length contiguous runs of segment_length elements
+        (None: one run of N) — the feature-major layout segment_sum produces, so h.cumsum(num_segments) is the cumulative
+        histogram of every feature.  Element i of the result is the sum of its run's elements from the run's start up to and
+        including i; with reverse=True, from i to the run's end.  Exponents follow the addition rule as for sum(): the exponent of
+        element i is the largest in its prefix and member j enters as ct_j^(2^(E_i - e_j)), so element i has the ciphertext and
+        exponent of self[a:i+1].sum() (self[i:b].sum() when reversed), bit for bit.
+        The outputs are NOT re-randomised (as sum() / segment_sum()) — the first element of a run is the input element itself:
+        call .apply_obfuscator() on the result before it leaves the party.  Runs on the key's device (pai_ct_scan: one Montgomery
+        product per element and one per exponent step, a second pass when the runs are too few to fill the device); no multi-GPU
+        fan-out.  Raises TypeError / ValueError for a segment_length that is not a positive integer dividing len(self)."""
+        n = self.__length
+        L = _cumsum_args(segment_length, n)
+        t, dom = self.__ipclCipherText._raw()
+        if n == 0:
+            return self._wrap(t, self._expo, 0, dom=dom)
+        h = self._h()
+        if abs(dom) > ADDN_RPOW_SPAN - 2:
+            t, dom = h.ct_retag(t, dom, 0), 0
+        raise_, step, out_expo = _scan_plan(self._expo, L, bool(reverse))
+        if raise_ is not None:
+            raise_, step = (torch.from_numpy(a).to(h.device) for a in (raise_, step))
+        # the result stays at domain tag 1, where the chain's products are closed: one product per element less than the wire form
+        out = h.ct_scan(t, L, tag=dom, dom_out=1, reverse=bool(reverse), raise_=raise_, step=step)
+        return self._wrap(out, out_expo, n, dom=1)
 
     def pack(self, *, slot_bits: int, value_bits: int, exponent: Optional[int] = None, slots: Optional[int] = None
              ) -> "PaillierPackedNumber":
