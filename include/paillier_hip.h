@@ -358,6 +358,14 @@ int pai_fp_unpack(const pai_pubkey* pk, const uint32_t* d_m, size_t G, int slot_
  * 2048 bits, wire-form input and batches of more output rows than the pai_path_edges(op 4) edge, one chain per lane on base-n
  * digit pairs (asynchronous; PAI_DISABLE=pack_padic leaves it out). */
 int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int slot_bits, int slots, uint32_t* d_out, void* stream);
+/* pai_ct_pack_step: the same chains with a free step — d_out[g] = prod_(j<count) d_ct[g count + j]^(2^(step_bits j)) mod n^2 in
+ * the wire form, G = ceil(N / count) rows, a ragged last chain multiplying only the rows it has.  With step_bits = k b it repacks
+ * packed rows of k slots of b bits: `count` consecutive rows become one row of count k slots (element i stays element i, in row
+ * i / (count k), slot i % (count k)); pai_ct_pack(b, k) is the case step_bits = b, count = k, with identical bits.  Constraints:
+ * step_bits >= 8, count >= 1 and count step_bits <= bits(n) - 2; anything else is PAI_E_INVALID and launches nothing.  Arguments,
+ * routes and knobs otherwise as pai_ct_pack (the hand-over counts output rows; PAI_DISABLE=pack_padic, PAI_TUNE pack_padic_min). */
+int pai_ct_pack_step(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int step_bits, int count, uint32_t* d_out,
+                     void* stream);
 
 /* Obfuscator randomness, replacing upstream ipcl's per-element getRandomBN inside
  * PublicKey::encrypt (called at classes.cpp:57): d_r[N][r_words] <- ChaCha20 key stream (RFC 8439 block

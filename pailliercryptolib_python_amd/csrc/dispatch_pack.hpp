@@ -1,4 +1,4 @@
-// pai_fp_pack / pai_fp_unpack / pai_ct_pack: packed ciphertexts, k fixed-point slots of b bits per plaintext (kernels_pack.hpp).
+// pai_fp_pack / pai_fp_unpack / pai_ct_pack / pai_ct_pack_step: packed ciphertexts, k fixed-point slots of b bits (kernels_pack.hpp).
 // (Part of the C-API translation unit: included by paillier_capi.hip inside extern "C", after dispatch_reduce.hpp.)
 #pragma once
 
@@ -48,14 +48,15 @@ int pai_fp_unpack(const pai_pubkey* pk, const uint32_t* d_m, size_t G, int slot_
     });
 }
 
-// Row g of the output is the Horner chain acc <- acc^(2^b) * ct[g k + j], j = len_g - 1 ... 0.
+// Row g of the output is the Horner chain acc <- acc^(2^step) * ct[g count + j], j = len_g - 1 ... 0 (pai_ct_pack: step = b,
+// count = k; pai_ct_pack_step: any step >= 8 with count step <= bits(n) - 2, the repacking of packed rows).
 // Route A (every key size): the member list (rows, steps, chain offsets) is written on the device (k_pack_plan) and run by the
 // level driver of pai_ct_segment_prod — k-member chains are cut into chunks when there are too few of them to fill the device,
-// and the partials joined at shift b * (chunk length).
+// and the partials joined at shift step * (chunk length).
 // Route B (keys the base-n digit engine serves, wire-form input, pack_padic_min_rows chains or more): the rows are brought to
 // digit form once (k_mexp_table_padic at one window bit: entry 0 = one, entry 1 = the ciphertext), then one chain per lane with
 // digit-pair squarings (k_ct_pack_padic).  false: the digit forms do not fit the device (the caller takes route A).
-static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32_t* d_ct, size_t N, int slot_bits, int slots, size_t G,
+static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32_t* d_ct, size_t N, int step, int count, size_t G,
                                  uint32_t* d_out) {
     const int pnl = pk->penc_nl;
     const size_t table_bytes = N * 2 * 2 * (size_t)pnl * 4;
@@ -74,7 +75,7 @@ static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint
     Q.table = pk->mexp_table.as<uint4>();
     Q.nd = pk->ct_nd;
     Q.ct_words = pk->ct_words;
-    Q.R = 1; Q.K = (int)N; Q.M = 1; Q.chunk = slots; Q.nsigns = 1;
+    Q.R = 1; Q.K = (int)N; Q.M = 1; Q.chunk = count; Q.nsigns = 1;
     Q.e_words = 1; Q.ebits_max = 1; Q.by_rows = 0;
     Q.wbits = 1;
     {
@@ -90,7 +91,7 @@ static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint
         const size_t tiles = (G + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
         ScopedKernelTimer t("k_ct_pack_padic", s);
-        if (!launch_ct_pack_padic(pnl, s, grid, Q, (int)N, slots, slot_bits, d_out, (int)G))
+        if (!launch_ct_pack_padic(pnl, s, grid, Q, (int)N, count, step, d_out, (int)G))
             throw PaiError(PAI_E_INTERNAL, "no pack kernel for this limb count");
         t.stop();
         HIP_CHECK(hipGetLastError());
@@ -99,35 +100,56 @@ static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint
     return true;
 }
 
+// The shared body of pai_ct_pack (step = slot_bits, count = slots) and pai_ct_pack_step: chains of `count` rows, `step` squarings
+// between members; the caller has checked count >= 1 and count * step <= bits(n) - 2.  Neither route ties the step to a slot:
+// k_ct_pack_padic squares `step` times between members, and k_segprod counts a member's shift down one squaring at a time in an
+// int — a chunk join carries the sum of its chunk's shifts, at most count * step < bits(n), so steps in the thousands of bits stay
+// far inside the driver's int32 shifts and the chunk length needs no clamp.
+static void ct_pack_body(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int step, int count, uint32_t* d_out,
+                         void* stream) {
+    require(N == 0 || (d_ct && d_out), "NULL argument");
+    require(std::abs(tag) <= RPOW_SPAN - 2, "pai_ct_pack: domain tag out of range");
+    require(N < ((size_t)1 << 31), "pai_ct_pack: too many rows for one call");
+    if (N == 0) return;
+    std::lock_guard<std::mutex> lk(pk->mu);
+    DeviceScope scope_(pk->device);
+    hipStream_t s = (hipStream_t)stream;
+    g_last_times.clear();
+    const size_t G = (N + (size_t)count - 1) / (size_t)count;
+    if (pk->penc_nl != 0 && tag == 0 && N < ((size_t)1 << 28) && !knob_disabled("pack_padic") &&
+        G >= pack_padic_min_rows((size_t)pk->dev.ncu) && ct_pack_padic_locked(pk, s, d_ct, N, step, count, G, d_out))
+        return;
+    uint32_t* rows;
+    int32_t* shift;
+    int64_t* offsets;
+    {
+        OrderScope order_(pk->order, s);
+        pk->pack_plan.ensure((G + 1) * sizeof(int64_t) + N * 8);
+        offsets = pk->pack_plan.as<int64_t>();
+        rows = reinterpret_cast<uint32_t*>(offsets + G + 1);
+        shift = reinterpret_cast<int32_t*>(rows + N);
+        hipLaunchKernelGGL(k_pack_plan, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, N, count, step, G, rows, shift, offsets);
+        HIP_CHECK(hipGetLastError());
+        order_.done();
+    }
+    segment_prod_locked(pk, s, d_ct, N, tag, rows, shift, offsets, G, d_out);
+}
+
 int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int slot_bits, int slots, uint32_t* d_out, void* stream) {
     return guarded([&] {
         require(pk != nullptr, "NULL argument");
         require_pack_layout(pk, slot_bits, slots);
-        require(N == 0 || (d_ct && d_out), "NULL argument");
-        require(std::abs(tag) <= RPOW_SPAN - 2, "pai_ct_pack: domain tag out of range");
-        require(N < ((size_t)1 << 31), "pai_ct_pack: too many rows for one call");
-        if (N == 0) return;
-        std::lock_guard<std::mutex> lk(pk->mu);
-        DeviceScope scope_(pk->device);
-        hipStream_t s = (hipStream_t)stream;
-        g_last_times.clear();
-        const size_t G = (N + (size_t)slots - 1) / (size_t)slots;
-        if (pk->penc_nl != 0 && tag == 0 && N < ((size_t)1 << 28) && !knob_disabled("pack_padic") &&
-            G >= pack_padic_min_rows((size_t)pk->dev.ncu) && ct_pack_padic_locked(pk, s, d_ct, N, slot_bits, slots, G, d_out))
-            return;
-        uint32_t* rows;
-        int32_t* shift;
-        int64_t* offsets;
-        {
-            OrderScope order_(pk->order, s);
-            pk->pack_plan.ensure((G + 1) * sizeof(int64_t) + N * 8);
-            offsets = pk->pack_plan.as<int64_t>();
-            rows = reinterpret_cast<uint32_t*>(offsets + G + 1);
-            shift = reinterpret_cast<int32_t*>(rows + N);
-            hipLaunchKernelGGL(k_pack_plan, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, N, slots, slot_bits, G, rows, shift, offsets);
-            HIP_CHECK(hipGetLastError());
-            order_.done();
-        }
-        segment_prod_locked(pk, s, d_ct, N, tag, rows, shift, offsets, G, d_out);
+        ct_pack_body(pk, d_ct, N, tag, slot_bits, slots, d_out, stream);
+    });
+}
+
+int pai_ct_pack_step(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int step_bits, int count, uint32_t* d_out,
+                     void* stream) {
+    return guarded([&] {
+        require(pk != nullptr, "NULL argument");
+        require(step_bits >= 8, "pai_ct_pack_step: step_bits must be at least 8");
+        require(count >= 1 && (long long)count * step_bits <= (long long)hbn::bitlen(pk->n) - 2,
+                "pai_ct_pack_step: count * step_bits must not exceed bits(n) - 2");
+        ct_pack_body(pk, d_ct, N, tag, step_bits, count, d_out, stream);
     });
 }

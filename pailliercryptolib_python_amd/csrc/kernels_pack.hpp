@@ -218,6 +218,7 @@ k_fp_unpack(const uint32_t* __restrict__ res, const uint32_t* __restrict__ n_wor
 }
 
 // The chains of pai_ct_pack as k_segprod members: chain g = rows g k + len - 1 ... g k (the highest slot first), every step b bits
+// (pai_ct_pack_step: k = the rows per chain, b = the step, whatever its width — the step is only ever copied into shift[])
 __global__ void __launch_bounds__(256)
 k_pack_plan(size_t N, int k, int b, size_t G, uint32_t* __restrict__ rows, int32_t* __restrict__ shift, int64_t* __restrict__ offsets) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1182,6 +1182,8 @@ k_smexp_padic(MexpPadicParams P, SmexpArgs S, const uint32_t* __restrict__ e, co
 // k_mexp_table_padic wrote with wbits = 1 (entry 0 of a row = one, entry 1 = the ciphertext).  The squarings are Padic::sqr_fused
 // (3.5 NL^2 limb products against the 8 NL^2 of a Montgomery product modulo n^2 on lane groups).  The wave runs all k slots: a
 // slot a lane does not have (the ragged last chain, dead lanes) multiplies by entry 0, and squarings of one stay one.
+// pai_ct_pack_step runs the same kernel with slots = the rows per chain and slot_bits = its step (a run-time trip count of the
+// squaring loop: a step of thousands of bits is a longer loop, nothing else).
 template <int NL, int U>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_ct_pack_padic(MexpPadicParams P, int nrows, int slots, int slot_bits, uint32_t* __restrict__ out, int nlanes) {

@@ -605,6 +605,18 @@ class PublicKeyHandle:
                                            _stream(self.device)))
         return out
 
+    def ct_pack_step(self, ct: torch.Tensor, step_bits: int, count: int, tag: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[N, W] rows at domain tag `tag` -> [ceil(N / count), W] wire form: out[g] = prod_(j<count) ct[g count + j]^(2^(step_bits j))
+        mod n^2 (pai_ct_pack_step: ct_pack with a step of any width >= 8, count step_bits <= bits(n) - 2 — the repacking of packed
+        rows).  Synchronises the current stream once (the plan's sizes)."""
+        self._chk(ct, self.ct_words, "ct")
+        if count < 1:
+            raise ValueError("count: expected a positive count")
+        out = self.empty_ct((ct.shape[0] + count - 1) // count) if out is None else out
+        _native.check(self.lib.pai_ct_pack_step(self.h, _ptr(ct), ct.shape[0], int(tag), int(step_bits), int(count), _ptr(out),
+                                                _stream(self.device)))
+        return out
+
     def draw_r(self, n: int, key: bytes, nonce: bytes, counter0: int = 0) -> torch.Tensor:
         """Obfuscator randomness on the device: ChaCha20 key stream under ``key`` (32 bytes, from the OS CSPRNG) and
         ``nonce`` (12 bytes).  DJN keys: r < 2^randbits.  Standard keys: rows of bits(n) random bits (candidates; the

@@ -15,6 +15,24 @@ The format (``include/paillier_hip.h``, "packed ciphertexts"; ``DESIGN.md`` sect
   max(v_a, v_b) + 1, multiplication by an integer c gives v + bit_length(|c|), and an operation whose bound would exceed b - 1
   raises ``OverflowError`` before any kernel runs.
 
+Row operations (``DESIGN.md`` section 2.13a).  A packed container of length N is a G x k matrix, G = ceil(N / k) rows (one
+ciphertext each), the tail slots of the last row 0; a product of rows modulo n^2 adds their plaintexts slot by slot, so the
+middle of a histogram pipeline runs on packed rows as it does on plain ciphertexts — with one exponent for the whole container
+(no alignment: every chain is pure products) and no bias (it appears only in ``pai_fp_unpack``):
+
+* ``rows``: G;
+* ``segment_sum(row_ids, num_segments)``: sums of rows by key, F * num_segments rows, feature-major (pai_ct_segment_prod);
+* ``cumsum(rows_per_run=None, reverse=False)``: prefix sums along runs of rows (pai_ct_scan);
+* ``sum()``: the one row that sums all of them (pai_ct_prod);
+* ``take(rows)``: the selected rows in the given order (a device gather, no arithmetic);
+* ``repack(factor=None)``: f consecutive rows become one row of k f slots, ``prod_(j<f) ct_(r f + j)^(2^(k b j))``
+  (pai_ct_pack_step) — element i stays element i, so the result is an ordinary packed container with fewer rows to decrypt.
+
+A sum of c members with |m| < 2^v satisfies |sum| < 2^(v + bit_length(c - 1)) (``sum_value_bits``): c is the largest member
+count of a segment, the run length, or G; like the arithmetic, an operation whose bound would exceed b - 1 raises
+``OverflowError`` before any Paillier kernel runs.  The results are canonical products, not re-randomised; they carry the
+inversion taint of their input, and a container without rows gives one without rows.
+
 Everything runs on the key's home device (no multi-GPU fan-out, as for ``segment_sum``).
 """
 from __future__ import annotations
@@ -27,6 +45,7 @@ import torch
 
 from . import engine
 from .bindings import ipclCipherText, merge_taint
+from .paillier import ADDN_RPOW_SPAN, _cumsum_args, _segment_ids, _segment_plan
 
 SLOT_BITS_MIN, SLOT_BITS_MAX = 8, 128
 
@@ -90,6 +109,45 @@ def add_value_bits(va: int, vb: int, slot_bits: int) -> int:
 def mul_value_bits(v: int, c: int, slot_bits: int) -> int:
     """|c m| < 2^(v + bit_length(|c|)); OverflowError when that exceeds slot_bits - 1."""
     return _headroom(int(v) + abs(int(c)).bit_length(), slot_bits, "multiplication")
+
+
+def sum_value_bits(v: int, count: int, slot_bits: int) -> int:
+    """|sum of `count` members| < 2^(v + bit_length(count - 1)) when every |m| < 2^v (count 2^v <= 2^(v + ceil(log2 count)));
+    OverflowError when that exceeds slot_bits - 1.  A sum of one member (or none) keeps v."""
+    return _headroom(int(v) + max(0, int(count) - 1).bit_length(), slot_bits, "sum")
+
+
+def repack_factor(n_bits: int, slot_bits: int, slots: int, factor: Optional[int] = None) -> int:
+    """The checked factor of repack(): f >= 1 rows of `slots` slots become one row, f slots slot_bits <= n_bits - 2 (default: the
+    largest such f; ValueError through layout() for one that does not fit)."""
+    f = max_slots(n_bits, slot_bits * slots) if factor is None else operator.index(factor)
+    if f < 1:
+        raise ValueError(f"repack: factor must be a positive integer, got {f}")
+    layout(n_bits, slot_bits, slots * f)
+    return f
+
+
+def _take_index(rows, G: int) -> np.ndarray:
+    """take()'s argument checks: a slice or a 1-D integer array / tensor -> int64 row indices in [0, G) (negative indices count from
+    the end, as in numpy).  TypeError / IndexError before anything is launched."""
+    if isinstance(rows, slice):
+        return np.arange(*rows.indices(G), dtype=np.int64)
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype.is_floating_point or rows.dtype.is_complex or rows.dtype == torch.bool:
+            raise TypeError(f"take: rows must have an integer dtype, got {rows.dtype}")
+        idx = rows.detach().cpu().numpy()
+    else:
+        idx = np.asarray(rows)
+        if idx.size == 0 and idx.dtype.kind == "f":      # an empty list
+            idx = idx.astype(np.int64)
+    if idx.dtype.kind not in "iu":
+        raise TypeError(f"take: rows must be a slice or an integer array, got dtype {idx.dtype}")
+    if idx.ndim != 1:
+        raise ValueError(f"take: rows must be 1-D, got shape {tuple(idx.shape)}")
+    if idx.size and (int(idx.max()) >= G or int(idx.min()) < -G):
+        raise IndexError(f"take: row index out of range for {G} rows")
+    idx = idx.astype(np.int64)
+    return np.where(idx < 0, idx + G, idx)
 
 
 def _as_batch(values, exponent: int, what: str) -> np.ndarray:
@@ -273,6 +331,30 @@ class PaillierPackedNumber:
         return PaillierPackedNumber(self.public_key, ipclCipherText(self.public_key.pubkey, ct, taint=taint), slot_bits=self.slot_bits,
                                     slots=self.slots, exponent=self.exponent, value_bits=value_bits, length=self.__length)
 
+    def _rows_like(self, ct, value_bits: int, *, slots: Optional[int] = None, length: Optional[int] = None, dom: int = 0
+                   ) -> "PaillierPackedNumber":
+        """The result of a row operation: rows `ct` (a device tensor at domain tag `dom`, or host words), whole rows of `slots`
+        slots unless `length` says otherwise; this container's inversion taint travels with it."""
+        k = self.slots if slots is None else slots
+        c = ipclCipherText(self.public_key.pubkey, ct, dom=dom, taint=self.__ct._taint)
+        return PaillierPackedNumber(self.public_key, c, slot_bits=self.slot_bits, slots=k, exponent=self.exponent,
+                                    value_bits=value_bits, length=c.getSize() * k if length is None else length)
+
+    def _no_rows(self):
+        return np.zeros((0, 2 * ((self.public_key.n.bit_length() + 31) // 32)), dtype=np.uint32)
+
+    def _tagged(self, h):
+        """(rows on the device, domain tag) for the chain runners that take tagged rows (a cumsum() result rests at tag 1)"""
+        t, dom = self.__ct._raw()
+        if abs(dom) > ADDN_RPOW_SPAN - 2:
+            t, dom = h.ct_retag(t, dom, 0), 0
+        return t, dom
+
+    @property
+    def rows(self) -> int:
+        """G: the ciphertexts of this container."""
+        return self.__ct.getSize()
+
     def apply_obfuscator(self, *, r: Optional[torch.Tensor] = None) -> None:
         """Re-randomise the G ciphertexts in place (pack() and the arithmetic below return canonical residues)."""
         pub = self.public_key.pubkey
@@ -369,3 +451,80 @@ class PaillierPackedNumber:
         for it in items[1:]:
             acc = acc + it
         return acc
+
+    # -- row operations (module docstring; slot-wise on the plaintexts) ------------------------------------------------------------
+    def segment_sum(self, row_ids, num_segments: int) -> "PaillierPackedNumber":
+        """Sums of rows by key: the encrypted histograms of GH-packed samples.  row_ids: an integer numpy array or torch tensor of
+        shape (G,) or (G, F), G = self.rows (the rules and errors of PaillierEncryptedNumber.segment_sum); a negative id drops
+        that (row, feature) pair.  The result has F * num_segments rows, feature-major: row f * num_segments + b is the product
+        modulo n^2 of the rows i with row_ids[i, f] == b, so each of its slots is the sum of that slot over those rows; an empty
+        segment gives the ciphertext 1 (all slots 0).  Same slot_bits, slots and exponent; value_bits grows by
+        bit_length(c - 1), c the largest member count of a segment (one scalar read from the plan), OverflowError before any
+        Paillier kernel when that leaves the slot.  The outputs are NOT re-randomised (as PaillierEncryptedNumber.segment_sum):
+        an empty bin is recognisable as 1 — call .apply_obfuscator() on the result before the histogram leaves the party."""
+        G = self.rows
+        ids = _segment_ids(row_ids, G, num_segments)
+        K = int(num_segments)
+        if G == 0:                                       # no rows in, no rows out (as every row operation)
+            return self._rows_like(self._no_rows(), self.value_bits)
+        h = self.public_key.pubkey.handle
+        # one exponent for the whole container: nothing to sort by, every shift 0 (NULL) — the chains are pure products
+        rows, _, offsets, _ = _segment_plan(ids.to(h.device), np.zeros(G, dtype=np.int64), K)
+        v = sum_value_bits(self.value_bits, int((offsets[1:] - offsets[:-1]).max()), self.slot_bits)
+        t, dom = self._tagged(h)
+        return self._rows_like(h.ct_segment_prod(t, rows, None, offsets, tag=dom), v)
+
+    def cumsum(self, rows_per_run: Optional[int] = None, *, reverse: bool = False) -> "PaillierPackedNumber":
+        """Prefix sums along rows: the G rows are G / rows_per_run contiguous runs (None: one run; the rules and errors of
+        PaillierEncryptedNumber.cumsum) — the feature-major layout segment_sum produces, so h.cumsum(num_segments) is the
+        cumulative histogram of every feature and slot.  Row i of the result is the product of its run's rows from the run's
+        start through i; with reverse=True, from i to the run's end.  The result has rows * slots elements (the tail slots of
+        the last row are sums now); value_bits grows by bit_length(rows_per_run - 1).  Not re-randomised: the first row of a
+        run is the input row itself.  (The rows rest at the Montgomery tag where pai_ct_scan's products are closed; whoever
+        reads them — ciphertext().getTexts(), pickling, decryption, the arithmetic — gets the wire form.)"""
+        G = self.rows
+        L = _cumsum_args(rows_per_run, G)
+        if G == 0:
+            return self._rows_like(self._no_rows(), self.value_bits)
+        v = sum_value_bits(self.value_bits, L, self.slot_bits)
+        h = self.public_key.pubkey.handle
+        t, dom = self._tagged(h)
+        return self._rows_like(h.ct_scan(t, L, tag=dom, dom_out=1, reverse=bool(reverse)), v, dom=1)
+
+    def sum(self) -> "PaillierPackedNumber":
+        """One row, the product of all G rows: slot j holds the sum of slot j over the rows (length `slots`); value_bits grows by
+        bit_length(G - 1).  Not re-randomised."""
+        G = self.rows
+        if G == 0:
+            return self._rows_like(self._no_rows(), self.value_bits)
+        v = sum_value_bits(self.value_bits, G, self.slot_bits)
+        h = self.public_key.pubkey.handle
+        return self._rows_like(h.ct_prod(self.__ct._t.contiguous(), 1), v)
+
+    def take(self, rows) -> "PaillierPackedNumber":
+        """The selected rows in the given order (the shuffle / split-candidate step of the protocol): `rows` is a slice or a 1-D
+        integer array or tensor of row indices (negative ones count from the end; IndexError outside [-G, G)).  A device gather
+        with no arithmetic: value_bits is unchanged, the result has len(rows) * slots elements."""
+        idx = _take_index(rows, self.rows)
+        if idx.size == 0:
+            return self._rows_like(self._no_rows(), self.value_bits)
+        t, dom = self.__ct._raw()
+        return self._rows_like(t.index_select(0, torch.from_numpy(idx).to(t.device)), self.value_bits, dom=dom)
+
+    def repack(self, *, factor: Optional[int] = None) -> "PaillierPackedNumber":
+        """`factor` consecutive rows become one row of slots * factor slots of the same width: output row r is
+        prod_(j<f) ct_(r f + j)^(2^(slots slot_bits j)) mod n^2 (pai_ct_pack_step), so element i stays element i — row
+        i // (slots f), slot i % (slots f) — and the result is an ordinary packed container of the same length with
+        ceil(G / f) rows to send and decrypt.  factor defaults to the largest that fits (f slots slot_bits <= bits(n) - 2); one
+        that does not fit is a ValueError.  value_bits is unchanged (no slot is added to); factor 1 returns a copy."""
+        f = repack_factor(self.public_key.n.bit_length(), self.slot_bits, self.slots, factor)
+        G = self.rows
+        if G == 0:
+            return self._rows_like(self._no_rows(), self.value_bits, slots=self.slots * f, length=0)
+        h = self.public_key.pubkey.handle
+        if f == 1:
+            t, dom = self.__ct._raw()
+            return self._rows_like(t.clone(), self.value_bits, length=self.__length, dom=dom)
+        t, dom = self._tagged(h)
+        out = h.ct_pack_step(t, self.slots * self.slot_bits, f, tag=dom)
+        return self._rows_like(out, self.value_bits, slots=self.slots * f, length=self.__length)
