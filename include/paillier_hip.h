@@ -367,6 +367,24 @@ int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, i
 int pai_ct_pack_step(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int step_bits, int count, uint32_t* d_out,
                      void* stream);
 
+/* pai_fp_quantize: a plaintext weight matrix at ONE common exponent as the operands of pai_ct_multiexp (R = 1) and
+ * pai_ct_sparse_multiexp — the linear maps of packed rows (PaillierPackedNumber.rmatmul / csr_rmatmul): a packed container has one
+ * exponent, so per-weight mantissa exponents are not allowed and every weight is rounded to the same grid.  A product of powers of
+ * packed rows, prod_l ct_l^(w_l) mod n^2, holds sum_l w_l m_(l,j) in slot j: with |m| < 2^v it satisfies |sum| <= (2^v - 1) S
+ * < 2^(v + bit_length(S)), S = sum_l |w_l| — the sums below are what the caller's headroom test needs before any Paillier kernel.
+ * Weight (l, j), l < K, j < M, is d_x[l stride_k + j stride_m] (strides in elements, either may be the unit one: X and X.T views go
+ * in without a copy); is_f64: doubles, w = rint(x 2^exponent), ties to even, formed on the 53-bit significand as in pai_fp_pack;
+ * else int64, w = x << exponent (exact).  d_e[(l M + j) e_words ..]: |w| in little-endian words; d_sign[l M + j] = (w < 0): the
+ * [K][M] operands of pai_ct_multiexp, at M = 1 the [T] operands of pai_ct_sparse_multiexp.  d_sum: exact sums of |w| as (low 64 bits,
+ * high 64 bits) pairs — d_offsets == NULL: one pair per column j, summed over l (M pairs); d_offsets: int64 [S + 1], nondecreasing
+ * (requires M = 1): one pair per segment [d_offsets[s], d_offsets[s + 1]) (S pairs; rows outside every segment count nowhere; S = 0 is allowed: words and signs only).  The
+ * call overwrites d_sum; a sum of 2^128 or more is stored as 2^128 - 1.  *d_flag (one device word the caller zeroes): bit 0 for some
+ * |w| >= 2^weight_bits (the operands are then undefined), bit 1 for a NaN or an infinity.  1 <= weight_bits <= min(126, 32 e_words),
+ * 1 <= e_words <= 4; anything else is PAI_E_INVALID and launches nothing.  Asynchronous on `stream`. */
+int pai_fp_quantize(const pai_pubkey* pk, const void* d_x, int is_f64, size_t K, size_t M, long long stride_k, long long stride_m,
+                    int exponent, int weight_bits, const int64_t* d_offsets, size_t S, uint32_t* d_e, int e_words, uint8_t* d_sign,
+                    uint64_t* d_sum, int32_t* d_flag, void* stream);
+
 /* Obfuscator randomness, replacing upstream ipcl's per-element getRandomBN inside
  * PublicKey::encrypt (called at classes.cpp:57): d_r[N][r_words] <- ChaCha20 key stream (RFC 8439 block
  * function; h_key8 = 256-bit key from the OS CSPRNG, h_nonce3 = 96-bit nonce, 32-bit block counter starting

@@ -95,6 +95,8 @@ PROTOTYPES = {
     "pai_fp_unpack": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, voidp, voidp, voidp]),
     "pai_ct_pack": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, C.c_int, voidp, voidp]),
     "pai_ct_pack_step": (C.c_int, [voidp, voidp, C.c_size_t, C.c_int, C.c_int, C.c_int, voidp, voidp]),
+    "pai_fp_quantize": (C.c_int, [voidp, voidp, C.c_int, C.c_size_t, C.c_size_t, C.c_longlong, C.c_longlong, C.c_int, C.c_int, voidp,
+                                  C.c_size_t, voidp, C.c_int, voidp, voidp, voidp, voidp]),
     "pai_draw_r": (C.c_int, [voidp, voidp, voidp, C.c_uint32, C.c_size_t, voidp, voidp]),
     "pai_modulus_create": (C.c_int, [voidp, C.c_int, C.c_int, C.POINTER(voidp)]),
     "pai_modulus_destroy": (None, [voidp]),

@@ -1,4 +1,5 @@
-// pai_fp_pack / pai_fp_unpack / pai_ct_pack / pai_ct_pack_step: packed ciphertexts, k fixed-point slots of b bits (kernels_pack.hpp).
+// pai_fp_pack / pai_fp_unpack / pai_ct_pack / pai_ct_pack_step / pai_fp_quantize: packed ciphertexts, k fixed-point slots of b bits
+// (kernels_pack.hpp).
 // (Part of the C-API translation unit: included by paillier_capi.hip inside extern "C", after dispatch_reduce.hpp.)
 #pragma once
 
@@ -151,5 +152,74 @@ int pai_ct_pack_step(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int t
         require(count >= 1 && (long long)count * step_bits <= (long long)hbn::bitlen(pk->n) - 2,
                 "pai_ct_pack_step: count * step_bits must not exceed bits(n) - 2");
         ct_pack_body(pk, d_ct, N, tag, step_bits, count, d_out, stream);
+    });
+}
+
+// Weights at one exponent as multi-exponentiation operands (kernels_pack.hpp: k_fp_quantize, k_fp_quantize_sums).  The limb sums
+// live on the handle's scratch (32 bytes per sum, zeroed here on the stream), so the call holds the handle's mutex like the chain
+// runners; nothing is read back.
+int pai_fp_quantize(const pai_pubkey* pk, const void* d_x, int is_f64, size_t K, size_t M, long long stride_k, long long stride_m,
+                    int exponent, int weight_bits, const int64_t* d_offsets, size_t S, uint32_t* d_e, int e_words, uint8_t* d_sign,
+                    uint64_t* d_sum, int32_t* d_flag, void* stream) {
+    return guarded([&] {
+        require(pk && d_flag, "NULL argument");
+        require(e_words >= 1 && e_words <= 4, "pai_fp_quantize: e_words must lie in 1 .. 4");
+        require(weight_bits >= 1 && weight_bits <= 126 && weight_bits <= 32 * e_words,
+                "pai_fp_quantize: weight_bits must lie in 1 .. min(126, 32 e_words)");
+        require(exponent > -(1 << 20) && exponent < (1 << 20), "exponent out of range");
+        require(d_offsets == nullptr || M == 1, "pai_fp_quantize: segment sums need M = 1");
+        require(K < ((size_t)1 << 31) && M < ((size_t)1 << 31) && S < ((size_t)1 << 31), "pai_fp_quantize: too many weights for one call");
+        const size_t nsums = d_offsets ? S : M;
+        require(nsums == 0 || d_sum, "NULL argument");
+        require(K * M == 0 || (d_x && d_e && d_sign), "NULL argument");
+        if (nsums == 0 && K * M == 0) return;              // (S = 0 with weights: words and signs are still written)
+        std::lock_guard<std::mutex> lk(pk->mu);
+        DeviceScope scope_(pk->device);
+        hipStream_t s = (hipStream_t)stream;
+        g_last_times.clear();
+        OrderScope order_(pk->order, s);
+        if (K * M == 0) {                                  // no weights: every sum is 0
+            HIP_CHECK(hipMemsetAsync(d_sum, 0, nsums * 16, s));
+            return;
+        }
+        pk->quant_acc.ensure(std::max<size_t>(nsums, 1) * 32);
+        if (nsums) HIP_CHECK(hipMemsetAsync(pk->quant_acc.p, 0, nsums * 32, s));
+        QuantArgs a;
+        a.x = reinterpret_cast<const uint64_t*>(d_x);
+        a.K = K; a.M = M; a.sk = stride_k; a.sm = stride_m;
+        a.E = exponent; a.wbits = weight_bits; a.ew = e_words;
+        a.tj_log2 = 0;
+        while (a.tj_log2 < 6 && ((size_t)1 << a.tj_log2) < M) ++a.tj_log2;
+        a.vec = (reinterpret_cast<uintptr_t>(d_e) & (size_t)(4 * e_words - 1)) == 0;
+        const size_t TJ = (size_t)1 << a.tj_log2, TL = QZ_THREADS / TJ, RM = std::max<size_t>(64, TL);
+        a.ncb = (M + TJ - 1) / TJ;
+        // about four workgroups per CU in all: long runs of rows per thread keep the sums in registers and the atomics few
+        // (PAI_TUNE quantize_blocks: the workgroup count aimed at — tests make one workgroup walk many tiles with it)
+        size_t blocks = (size_t)4 * pk->dev.ncu;
+        if (long long v; knob_tune("quantize_blocks", &v) && v > 0) blocks = (size_t)v;
+        const size_t macros = (K + RM - 1) / RM, want = std::max<size_t>(1, blocks / a.ncb);
+        a.rows_per_block = (macros + std::min(macros, want) - 1) / std::min(macros, want) * RM;
+        const size_t nrb = (K + a.rows_per_block - 1) / a.rows_per_block;
+        require(nrb * a.ncb < ((size_t)1 << 31), "pai_fp_quantize: too many weights for one call");
+        a.offsets = d_offsets; a.S = S;
+        a.e = d_e; a.sign = d_sign;
+        a.acc = pk->quant_acc.as<unsigned long long>();
+        a.flag = d_flag;
+        const bool via_lds = M > 1 && stride_k == 1 && stride_m != 1;
+        const dim3 grid((unsigned)(nrb * a.ncb)), block(QZ_THREADS);
+        ScopedKernelTimer t("k_fp_quantize", s);
+        if (is_f64) {
+            if (via_lds) hipLaunchKernelGGL((k_fp_quantize<true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_fp_quantize<true, false>), grid, block, 0, s, a);
+        } else {
+            if (via_lds) hipLaunchKernelGGL((k_fp_quantize<false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_fp_quantize<false, false>), grid, block, 0, s, a);
+        }
+        HIP_CHECK(hipGetLastError());
+        if (nsums)
+            hipLaunchKernelGGL(k_fp_quantize_sums, dim3((unsigned)((nsums + 255) / 256)), dim3(256), 0, s, a.acc, nsums, d_sum);
+        t.stop();
+        HIP_CHECK(hipGetLastError());
+        order_.done();
     });
 }

@@ -2,6 +2,8 @@
 //   k_fp_pack     float64 / int64 [N] -> residues [G][nw] of P_g = sum_j m_(g k + j) 2^(b j) mod n,  G = ceil(N / k)
 //   k_fp_unpack   residues [G][nw] -> signed mantissas [G k] (int64 for b <= 64, (low uint64, high int64) pairs above)
 //   k_pack_plan   the member list of pai_ct_pack's Horner chains for k_segprod (rows in descending slot order, every shift = b)
+//   k_fp_quantize float64 / int64 weights [K][M] at any strides -> |w| words [K][M][ew], signs [K][M] and exact sums of |w| per column
+//                 or per segment: the operands of pai_ct_multiexp / pai_ct_sparse_multiexp at one common exponent (packed rows)
 // The format: element i lives in row i / k, slot i % k, bits [j b, (j + 1) b); with the bias B = sum_j 2^(b - 1) 2^(b j) the
 // biased row Q = P + B has the unsigned fields m_j + 2^(b - 1) side by side, so no borrow crosses a slot: pack writes Q - B
 // (+ n when P < 0), unpack reads the fields of (residue + B) mod n.  k b <= bits(n) - 2, hence |P| < n / 4 and one conditional
@@ -71,20 +73,21 @@ struct BitWindow {
 // The signed mantissa of element i at exponent E as a 128-bit two's-complement pair (lo, hi); status bits as pai_fp_pack's flag:
 // 1 = |mantissa| >= 2^vbits, 2 = NaN or infinity.  float64: rint(x 2^E), ties to even, exact for every finite x (the product is
 // formed on the 53-bit significand, not in floating point); int64: x << E.
+// (raw: the 64 bits of the double or of the int64 — k_fp_quantize hands its values over from LDS.)
 template <bool IS_F64>
-__device__ __forceinline__ int pack_mantissa(const void* __restrict__ x_, size_t i, int E, int vbits, uint64_t& lo, uint64_t& hi) {
+__device__ __forceinline__ int pack_mantissa_raw(uint64_t raw, int E, int vbits, uint64_t& lo, uint64_t& hi) {
     uint64_t mag;
     bool neg;
     long long q;                                       // the value is +-mag 2^q
     if constexpr (IS_F64) {
-        const uint64_t bits = (uint64_t)__double_as_longlong(reinterpret_cast<const double*>(x_)[i]);
+        const uint64_t bits = raw;
         const int e = (int)((bits >> 52) & 0x7FF);
         neg = bits >> 63;
         if (e == 0x7FF) { lo = hi = 0; return 2; }
         mag = e ? ((bits & 0xFFFFFFFFFFFFFull) | (1ull << 52)) : (bits & 0xFFFFFFFFFFFFFull);
         q = (long long)(e ? e : 1) - 1075 + E;
     } else {
-        const int64_t v = reinterpret_cast<const int64_t*>(x_)[i];
+        const int64_t v = (int64_t)raw;
         neg = v < 0;
         mag = neg ? (0ull - (uint64_t)v) : (uint64_t)v;
         q = E;
@@ -118,6 +121,11 @@ __device__ __forceinline__ int pack_mantissa(const void* __restrict__ x_, size_t
         hi = mhi;
     }
     return bad;
+}
+
+template <bool IS_F64>
+__device__ __forceinline__ int pack_mantissa(const void* __restrict__ x_, size_t i, int E, int vbits, uint64_t& lo, uint64_t& hi) {
+    return pack_mantissa_raw<IS_F64>(reinterpret_cast<const uint64_t*>(x_)[i], E, vbits, lo, hi);
 }
 
 // One lane per output row.  The sign of P is that of its highest non-zero slot (the slots below sum to less than 2^(b j)), so
@@ -229,6 +237,152 @@ k_pack_plan(size_t N, int k, int b, size_t G, uint32_t* __restrict__ rows, int32
         shift[i] = b;
     }
     if (i <= G) offsets[i] = (int64_t)(i * (size_t)k < N ? i * (size_t)k : N);
+}
+
+// ---- pai_fp_quantize: a weight matrix at ONE exponent as multi-exponentiation operands ---------------------------------------------
+// Weight (l, j) = x[l sk + j sm] -> w = rint(x 2^E) (pack_mantissa_raw), |w| to e[(l M + j) ew ..], w < 0 to sign[l M + j], and the
+// sum of |w| over l per column j (or, offsets given and M = 1, per segment [offsets[s], offsets[s + 1])).
+// A workgroup owns TJ = 2^tj_log2 columns (the smallest power of two >= min(M, 64)) and a run of rows; thread t works on column
+// t % TJ and rows t / TJ + n TL, TL = 256 / TJ, so the words and signs leave with the lanes along j — the order they are stored in.
+// The loads run along j too when sm is the unit stride (DIRECT).  When sk is (VIA_LDS) a tile of RM = max(64, TL) rows x TJ columns
+// is loaded with the lanes along l and read back transposed from LDS; the pitch RM + 1 (in 8-byte words) spreads the 32 lanes of a
+// ds_read_b64 group over all 64 banks.
+// Sums: |w| < 2^126 and up to 2^28 rows need 154 bits, so a sum is kept as four sums of 32-bit limbs (each < 2^60: no 64-bit word can
+// wrap) and put together by k_fp_quantize_sums.  Column mode: a thread keeps the limb sums of its column in registers over all its
+// rows, the lanes of a wave that share a column are folded by shuffles (strides TJ, 2 TJ, ...), the four waves through LDS, and one
+// lane per column and workgroup adds to acc[].  Segment mode (TJ = 1, lanes along l, the segment of a row by bisection of offsets):
+// a segmented inclusive scan over the wave, the last lane of each run adds.  acc[]: [sums][4] 64-bit words, zeroed by the caller.
+constexpr int QZ_THREADS = 256;
+constexpr int QZ_TILE_WORDS = 64 * 65;                 // TJ (RM + 1) at its largest: 64 x 65 (2 x 129, 4 x 65, ... are smaller)
+
+struct QuantArgs {
+    const uint64_t* x;                                 // the 64 bits of every weight
+    size_t K, M;
+    long long sk, sm;                                  // strides in elements
+    int E, wbits, ew, tj_log2, vec;                    // vec: e is 8-byte (ew = 2) / 16-byte (ew = 4) aligned
+    size_t rows_per_block, ncb;                        // a multiple of RM; column blocks
+    const int64_t* offsets;                            // NULL: column sums
+    size_t S;
+    uint32_t* e;
+    uint8_t* sign;
+    unsigned long long* acc;
+    int32_t* flag;
+};
+
+template <bool IS_F64, bool VIA_LDS>
+__global__ void __launch_bounds__(QZ_THREADS)
+k_fp_quantize(QuantArgs a) {
+    __shared__ uint64_t tile[VIA_LDS ? QZ_TILE_WORDS : 1];
+    __shared__ unsigned long long red[QZ_THREADS / 64][64][4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int TJ = 1 << a.tj_log2, TL = QZ_THREADS >> a.tj_log2, RM = TL > 64 ? TL : 64;
+    const int tj = t & (TJ - 1), tl = t >> a.tj_log2;
+    const size_t cb = (size_t)blockIdx.x % a.ncb, rb = (size_t)blockIdx.x / a.ncb;
+    const size_t j0 = cb * (size_t)TJ, j = j0 + (size_t)tj;
+    const size_t l_begin = rb * a.rows_per_block;
+    const size_t l_end = a.K - l_begin < a.rows_per_block ? a.K : l_begin + a.rows_per_block;
+    const bool col_ok = j < a.M;
+    const long long S = (long long)a.S;
+    unsigned long long sum[4] = {0, 0, 0, 0};
+    int st = 0;
+    for (size_t lm = l_begin; lm < l_end; lm += (size_t)RM) {
+        if constexpr (VIA_LDS) {
+            const int rm_log2 = 31 - __clz(RM);
+            for (int idx = t; idx < RM * TJ; idx += QZ_THREADS) {
+                const int ll = idx & (RM - 1), jj = idx >> rm_log2;
+                const size_t l = lm + (size_t)ll, jc = j0 + (size_t)jj;
+                if (l < l_end && jc < a.M) tile[jj * (RM + 1) + ll] = a.x[(long long)l * a.sk + (long long)jc * a.sm];
+            }
+            __syncthreads();
+        }
+        for (int p = tl; p < RM; p += TL) {            // RM / TL trips for every thread
+            const size_t l = lm + (size_t)p;
+            const bool ok = col_ok && l < l_end;
+            uint64_t mlo = 0, mhi = 0;
+            if (ok) {
+                uint64_t raw;
+                if constexpr (VIA_LDS) raw = tile[tj * (RM + 1) + p];
+                else raw = a.x[(long long)l * a.sk + (long long)j * a.sm];
+                uint64_t lo, hi;
+                st |= pack_mantissa_raw<IS_F64>(raw, a.E, a.wbits, lo, hi);
+                const bool neg = hi >> 63;
+                mlo = neg ? 0ull - lo : lo;
+                mhi = neg ? ~hi + (lo == 0 ? 1ull : 0ull) : hi;
+                const size_t o = l * a.M + j;
+                uint32_t* w = a.e + o * (size_t)a.ew;
+                if (a.ew == 1) w[0] = (uint32_t)mlo;
+                else if (a.ew == 2 && a.vec) *reinterpret_cast<uint2*>(w) = make_uint2((uint32_t)mlo, (uint32_t)(mlo >> 32));
+                else if (a.ew == 4 && a.vec)
+                    *reinterpret_cast<uint4*>(w) = make_uint4((uint32_t)mlo, (uint32_t)(mlo >> 32), (uint32_t)mhi, (uint32_t)(mhi >> 32));
+                else
+                    for (int i = 0; i < a.ew; ++i) w[i] = (uint32_t)((i < 2 ? mlo : mhi) >> (32 * (i & 1)));
+                a.sign[o] = neg ? 1 : 0;
+            }
+            const unsigned long long limb[4] = {mlo & 0xFFFFFFFFull, mlo >> 32, mhi & 0xFFFFFFFFull, mhi >> 32};
+            if (a.offsets == nullptr) {
+                for (int i = 0; i < 4; ++i) sum[i] += limb[i];
+            } else {
+                // the segment of row l: (entries of offsets[0 .. S] that are <= l) - 1; rows of no segment get -1 / S, which keeps
+                // the keys of a wave nondecreasing
+                long long seg = S;
+                if (ok) {
+                    long long lo_ = 0, hi_ = S + 1;
+                    while (lo_ < hi_) {
+                        const long long mid = (lo_ + hi_) >> 1;
+                        if (a.offsets[mid] <= (long long)l) lo_ = mid + 1; else hi_ = mid;
+                    }
+                    seg = lo_ - 1;
+                }
+                unsigned long long v[4] = {limb[0], limb[1], limb[2], limb[3]};
+                for (int d = 1; d < 64; d <<= 1) {
+                    const long long oseg = __shfl_up(seg, d);
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned long long ov = __shfl_up(v[i], d);
+                        if (lane >= d && oseg == seg) v[i] += ov;
+                    }
+                }
+                const long long nseg = __shfl_down(seg, 1);
+                if ((lane == 63 || nseg != seg) && seg >= 0 && seg < S)
+                    for (int i = 0; i < a.ew; ++i)
+                        if (v[i]) atomicAdd(a.acc + (size_t)seg * 4 + i, v[i]);
+            }
+        }
+        if constexpr (VIA_LDS) __syncthreads();        // the tile is free for the next load
+    }
+    if (a.offsets == nullptr) {
+        for (int d = TJ; d < 64; d <<= 1)
+            for (int i = 0; i < 4; ++i) {
+                const unsigned long long ov = __shfl_down(sum[i], d);
+                if (lane + d < 64) sum[i] += ov;
+            }
+        if (lane < TJ)
+            for (int i = 0; i < 4; ++i) red[wave][lane][i] = sum[i];
+        __syncthreads();
+        if (wave == 0 && lane < TJ && col_ok)
+            for (int i = 0; i < a.ew; ++i) {
+                const unsigned long long v = red[0][lane][i] + red[1][lane][i] + red[2][lane][i] + red[3][lane][i];
+                if (v) atomicAdd(a.acc + j * 4 + i, v);
+            }
+    }
+    if (st) atomicOr(a.flag, st);
+}
+
+// acc[s] = the four limb sums of sum s -> sum[s] = (low, high) 64 bits of a0 + a1 2^32 + a2 2^64 + a3 2^96; a total of 2^128 or
+// more is stored as 2^128 - 1 (it fails every headroom test a caller can make: slots have at most 128 bits)
+__global__ void __launch_bounds__(256)
+k_fp_quantize_sums(const unsigned long long* __restrict__ acc, size_t n, uint64_t* __restrict__ sum) {
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint64_t a0 = acc[4 * s], a1 = acc[4 * s + 1], a2 = acc[4 * s + 2], a3 = acc[4 * s + 3];
+    uint64_t lo = a0 + (a1 << 32);
+    uint64_t hi = (a1 >> 32) + (lo < a0 ? 1ull : 0ull);                    // < 2^33
+    bool over = (a3 >> 32) != 0;
+    uint64_t h2 = hi + a2;
+    over |= h2 < hi;
+    hi = h2 + (a3 << 32);
+    over |= hi < h2;
+    sum[2 * s] = over ? ~0ull : lo;
+    sum[2 * s + 1] = over ? ~0ull : hi;
 }
 
 }  // namespace pai

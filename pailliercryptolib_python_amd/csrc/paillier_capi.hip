@@ -375,7 +375,8 @@ struct ScopedKernelTimer {
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
-//                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels)
+//                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels),
+//                                  quantize_blocks (workgroups pai_fp_quantize aims at; default 4 per CU)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -516,6 +517,7 @@ struct pai_pubkey {
     mutable DevBuf smexp_plan;                 // segment offsets and chunk plan of pai_ct_sparse_multiexp
     mutable DevBuf seg_partial, seg_plan;      // chunk partials and chunk plans of pai_ct_segment_prod
     mutable DevBuf pack_plan;                  // member list of pai_ct_pack (rows, steps, chain offsets)
+    mutable DevBuf quant_acc;                  // limb sums of pai_fp_quantize (four 64-bit words per column / segment)
     uint32_t* d_nsq_words = nullptr;   // n^2 as packed words (extended-GCD modulus)
     mutable DevBuf table, tmp;    // standard-scheme scratch
     mutable DevBuf inv_prod, inv_inv, inv_fail;
@@ -1134,6 +1136,7 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     pk->seg_partial.release();
     pk->seg_plan.release();
     pk->pack_plan.release();
+    pk->quant_acc.release();
     if (pk->d_nsq_words) (void)hipFree(pk->d_nsq_words);
     if (pk->d_tree_c) (void)hipFree(pk->d_tree_c);
     if (pk->d_tree_fix) (void)hipFree(pk->d_tree_fix);
@@ -1191,6 +1194,7 @@ int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
         pk->seg_partial.release();
         pk->seg_plan.release();
         pk->pack_plan.release();
+        pk->quant_acc.release();
         pk->inv_prod.release();
         pk->inv_inv.release();
         pk->prod_a.release();

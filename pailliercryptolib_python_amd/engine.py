@@ -617,6 +617,30 @@ class PublicKeyHandle:
                                                 _stream(self.device)))
         return out
 
+    def fp_quantize(self, x: torch.Tensor, exponent: int, weight_bits: int, e_words: int, offsets: Optional[torch.Tensor] = None):
+        """float64 / int64 weights [K, M] (any strides: a transposed view goes in as it is) or [K] on the device -> (|w| words int32
+        [K, M, e_words], signs uint8 [K, M], sums of |w| int64 [M, 2] = (low, high 64 bits) per column, flag int32 [1]) with
+        w = rint(x 2^exponent) / x << exponent (pai_fp_quantize); flag bit 0: some |w| >= 2^weight_bits, bit 1: NaN / infinity.
+        offsets (int64 [S + 1], x of shape [K]): the sums are per segment, [S, 2]; words and signs are [K, e_words] and [K]."""
+        if x.dtype not in (torch.float64, torch.int64) or x.dim() not in (1, 2) or x.device != self.device:
+            raise ValueError("x: expected float64 / int64 [K, M] or [K] on %s" % self.device)
+        K = x.shape[0]
+        M = x.shape[1] if x.dim() == 2 else 1
+        sk, sm = (x.stride(0), x.stride(1)) if x.dim() == 2 else (x.stride(0), 1)
+        if offsets is not None:
+            if x.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or not offsets.is_contiguous() \
+                    or offsets.device != self.device:
+                raise ValueError("offsets: expected contiguous int64 [S + 1] on %s beside weights of shape [K]" % self.device)
+        S = 0 if offsets is None else offsets.shape[0] - 1
+        e = torch.empty((K, M, e_words) if x.dim() == 2 else (K, e_words), dtype=torch.int32, device=self.device)
+        sign = torch.empty((K, M) if x.dim() == 2 else (K,), dtype=torch.uint8, device=self.device)
+        sums = torch.empty((M if offsets is None else S, 2), dtype=torch.int64, device=self.device)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.pai_fp_quantize(self.h, _ptr(x), 1 if x.dtype == torch.float64 else 0, K, M, sk, sm, int(exponent),
+                                               int(weight_bits), _ptr(offsets), S, _ptr(e), int(e_words), _ptr(sign), _ptr(sums),
+                                               _ptr(flag), _stream(self.device)))
+        return e, sign, sums, flag
+
     def draw_r(self, n: int, key: bytes, nonce: bytes, counter0: int = 0) -> torch.Tensor:
         """Obfuscator randomness on the device: ChaCha20 key stream under ``key`` (32 bytes, from the OS CSPRNG) and
         ``nonce`` (12 bytes).  DJN keys: r < 2^randbits.  Standard keys: rows of bits(n) random bits (candidates; the

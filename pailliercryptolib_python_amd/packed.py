@@ -33,6 +33,23 @@ count of a segment, the run length, or G; like the arithmetic, an operation whos
 ``OverflowError`` before any Paillier kernel runs.  The results are canonical products, not re-randomised; they carry the
 inversion taint of their input, and a container without rows gives one without rows.
 
+Linear maps of rows (``DESIGN.md`` section 2.13b).  A product of POWERS of rows forms ``sum_i w_i P_i`` slot by slot, so a plaintext
+matrix acts on the rows of a container — the encrypted gradient ``X.T @ [[D]]`` of a linear model with the k residual columns of a
+sample in the k slots of its row, one multi-exponentiation per feature instead of k:
+
+* ``scale_rows(c)``: row i becomes ``ct_i^(c_i)`` for integers c_i (pai_ct_mul; negative ones through the inverse);
+* ``rmatmul(W, weight_exponent=0)`` / ``W @ packed``: W dense (F, G) or (G,), output row f = ``prod_i ct_i^(w_fi)``
+  (pai_fp_quantize, then pai_ct_multiexp);
+* ``csr_rmatmul(indptr, indices, data, shape, weight_exponent=0)`` / ``A @ packed`` for a scipy sparse A: the same over the stored
+  entries of a CSR matrix (pai_fp_quantize per segment, then pai_ct_sparse_multiexp).
+
+A container has ONE exponent, so every weight is brought to one grid: integer dtypes exactly, w = x << weight_exponent, float
+dtypes as w = rint(x 2^weight_exponent) (ties to even), and the result's exponent is E + weight_exponent.  With |m| < 2^v a weighted
+sum satisfies |sum_i w_i m_i| <= (2^v - 1) S < 2^(v + bit_length(S)), S = sum_i |w_i| (``weighted_sum_value_bits``); S is the largest
+such sum of an output row, read from the device before any Paillier kernel runs (two read-backs per product: the extremes of
+the weights, which give the exact exponent width of the multi-exponentiation, then the sums).  ``packed @ W`` is a TypeError: a
+matrix on the right would have to split rows, which no operation on ciphertexts can do.
+
 Everything runs on the key's home device (no multi-GPU fan-out, as for ``segment_sum``).
 """
 from __future__ import annotations
@@ -43,11 +60,16 @@ from typing import List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import engine
+from . import _native, engine
 from .bindings import ipclCipherText, merge_taint
-from .paillier import ADDN_RPOW_SPAN, _cumsum_args, _segment_ids, _segment_plan
+from .paillier import (ADDN_RPOW_SPAN, PaillierEncryptedNumber, _csr_args, _cumsum_args, _host_array, _scipy_sparse, _segment_ids,
+                       _segment_plan)
 
 SLOT_BITS_MIN, SLOT_BITS_MAX = 8, 128
+WEIGHT_BITS_MAX = 126           # the widest |w| pai_fp_quantize forms
+# routes taken by rmatmul / csr_rmatmul since import: "fast" = pai_ct_multiexp / pai_ct_sparse_multiexp, "composite" = gather,
+# pai_ct_mul and pai_ct_segment_prod (the defining route)
+PACKED_ROUTES = {"fast": 0, "composite": 0}
 
 
 class Layout(NamedTuple):
@@ -115,6 +137,98 @@ def sum_value_bits(v: int, count: int, slot_bits: int) -> int:
     """|sum of `count` members| < 2^(v + bit_length(count - 1)) when every |m| < 2^v (count 2^v <= 2^(v + ceil(log2 count)));
     OverflowError when that exceeds slot_bits - 1.  A sum of one member (or none) keeps v."""
     return _headroom(int(v) + max(0, int(count) - 1).bit_length(), slot_bits, "sum")
+
+
+def weighted_sum_value_bits(v: int, abs_sum: int, slot_bits: int) -> int:
+    """|sum_i w_i m_i| <= (2^v - 1) S < 2^(v + bit_length(S)) when every |m_i| < 2^v and S = sum_i |w_i| = abs_sum (S = 0 keeps v);
+    OverflowError when that exceeds slot_bits - 1."""
+    S = int(abs_sum)
+    if S < 0:
+        raise ValueError("weighted_sum_value_bits: abs_sum is a sum of magnitudes")
+    return _headroom(int(v) + S.bit_length(), slot_bits, "weighted sum")
+
+
+def _weight_exponent(weight_exponent) -> int:
+    if isinstance(weight_exponent, (bool, np.bool_)) or not isinstance(weight_exponent, (int, np.integer)):
+        raise TypeError(f"weight_exponent must be an integer, got {type(weight_exponent).__name__}")
+    return int(weight_exponent)
+
+
+def _weights(x, what: str, weight_exponent: int) -> torch.Tensor:
+    """A weight array of a caller (numpy, list or torch on any device) as a float64 / int64 torch tensor of the same shape and,
+    for tensors, on its own device.  TypeError for bool, complex and object dtypes; ValueError for integers that do not fit 64
+    signed bits or come with a negative weight_exponent."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bool or x.dtype.is_complex:
+            raise TypeError(f"{what}: weights must be integers or floats, got {x.dtype}")
+        if x.dtype == getattr(torch, "uint64", None):
+            x = torch.from_numpy(_host_array(x, what))
+        t = x.detach()
+    else:
+        a = np.asarray(x)
+        if a.dtype.kind not in "fiu":
+            raise TypeError(f"{what}: weights must be integers or floats, got dtype {a.dtype}")
+        if a.dtype == np.uint64:
+            if a.size and int(a.max()) >= 1 << 63:
+                raise ValueError(f"{what}: integer weights must fit 64 signed bits")
+            a = a.astype(np.int64)
+        if a.dtype == np.float16 or (a.dtype.kind == "f" and a.dtype.itemsize > 8):
+            a = a.astype(np.float64)
+        t = torch.from_numpy(np.ascontiguousarray(a)) if a.size else torch.zeros(a.shape, dtype=torch.float64 if a.dtype.kind == "f"
+                                                                                   else torch.int64)
+    if t.dtype.is_floating_point:
+        return t.to(torch.float64)
+    if weight_exponent < 0:
+        raise ValueError(f"{what}: integer weights need a weight_exponent >= 0")
+    return t.to(torch.int64)
+
+
+def _weight_bits(t: torch.Tensor, weight_exponent: int, what: str) -> int:
+    """The bit length of the largest |w| of a checked weight tensor (>= 1), from its extremes (one read-back): ValueError for a NaN
+    or an infinity, OverflowError past WEIGHT_BITS_MAX."""
+    if t.numel() == 0:
+        return 1
+    lo, hi = torch.stack([t.min(), t.max()]).tolist()
+    if t.dtype.is_floating_point:
+        from fractions import Fraction
+
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f"{what}: NaN or infinity among the weights")
+        top = round(Fraction(max(abs(lo), abs(hi))) * Fraction(2) ** weight_exponent)      # ties to even, as the device rounds
+    else:
+        top = max(abs(int(lo)), abs(int(hi))) << weight_exponent
+    bits = max(1, int(top).bit_length())
+    if bits > WEIGHT_BITS_MAX:
+        raise OverflowError(f"{what}: a weight of {bits} bits at weight_exponent {weight_exponent} (|w| < 2^{WEIGHT_BITS_MAX} is served)")
+    return bits
+
+
+def _mexp_min_terms() -> int:
+    import os
+
+    try:
+        return int(os.environ.get("PAI_MEXP_MIN_TERMS", PaillierEncryptedNumber.MEXP_MIN_TERMS))
+    except ValueError:
+        return PaillierEncryptedNumber.MEXP_MIN_TERMS
+
+
+def _row_multipliers(c, rows: int) -> np.ndarray:
+    """scale_rows' argument checks: a 1-D integer array / tensor of length `rows` -> int64 (TypeError / ValueError before any launch)."""
+    if isinstance(c, torch.Tensor):
+        if c.dtype.is_floating_point or c.dtype.is_complex or c.dtype == torch.bool:
+            raise TypeError(f"scale_rows: multipliers must have an integer dtype, got {c.dtype}")
+        a = _host_array(c, "scale_rows")
+    else:
+        a = np.asarray(c)
+        if a.size == 0 and a.dtype.kind == "f":          # an empty list
+            a = a.astype(np.int64)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"scale_rows: multipliers must have an integer dtype, got {a.dtype}")
+    if a.ndim != 1 or a.shape[0] != rows:
+        raise ValueError(f"scale_rows: expected {rows} multipliers (one per row), got shape {tuple(a.shape)}")
+    if a.dtype == np.uint64 and a.size and int(a.max()) >= 1 << 63:
+        raise ValueError("scale_rows: multipliers must fit 64 signed bits")
+    return np.ascontiguousarray(a.astype(np.int64))
 
 
 def repack_factor(n_bits: int, slot_bits: int, slots: int, factor: Optional[int] = None) -> int:
@@ -528,3 +642,178 @@ class PaillierPackedNumber:
         t, dom = self._tagged(h)
         out = h.ct_pack_step(t, self.slots * self.slot_bits, f, tag=dom)
         return self._rows_like(out, self.value_bits, slots=self.slots * f, length=self.__length)
+
+    # -- linear maps of rows (module docstring) -----------------------------------------------------------
+    def __array__(self, dtype=None, copy=None):
+        """A 0-d object array holding self (as PaillierEncryptedNumber.__array__): scipy's `A @ packed` then returns NotImplemented
+        and Python calls __rmatmul__."""
+        a = np.empty((), dtype=object)
+        a[()] = self
+        return a
+
+    def _pow_rows(self, h, ct: torch.Tensor, e: torch.Tensor, sign: Optional[torch.Tensor], bits: int, taint: tuple):
+        """(ct_i^(+-e_i), taint): e int32 [N, ew] magnitudes on the device, sign bool [N] or None (all non-negative): the rows with
+        a negative multiplier are inverted first (pai_ct_invert_flag, its word joins the taint), then one pai_ct_mul."""
+        if sign is not None:
+            idx = torch.nonzero(sign).reshape(-1)
+            if idx.numel():
+                flag = h.new_flag()
+                taint = merge_taint(taint, (flag,))
+                if idx.numel() == ct.shape[0]:
+                    ct = h.ct_invert(ct, flag=flag)
+                else:
+                    ct = ct.clone()
+                    ct[idx] = h.ct_invert(ct[idx].contiguous(), flag=flag)
+        return h.ct_mul(ct, e, bits), taint              # on the home device, as everything here (no fan-out)
+
+    def scale_rows(self, c) -> "PaillierPackedNumber":
+        """Row i becomes ct_i^(c_i) mod n^2: every slot of row i is multiplied by the integer c_i.  c: a 1-D integer array or tensor
+        of length `rows` (TypeError for floats or bools, ValueError for another length).  A negative c_i goes through the inverse of
+        the row (the inversion's outcome travels with the result, as for `* -1`), c_i = 0 gives the ciphertext 1.  value_bits
+        becomes v + bit_length(max |c_i|), OverflowError before any launch when that leaves the slot.  Not re-randomised (a row
+        with c_i = 0 or 1 is recognisable): call .apply_obfuscator() on the result before it leaves the party."""
+        G = self.rows
+        c64 = _row_multipliers(c, G)
+        if G == 0:
+            return self._rows_like(self._no_rows(), self.value_bits)
+        mag = np.abs(c64).view(np.uint64)                # (|-2^63| wraps back to the bit pattern of 2^63)
+        bits = int(mag.max()).bit_length()
+        v = _headroom(self.value_bits + bits, self.slot_bits, "scale_rows")
+        h = self.public_key.pubkey.handle
+        ew = (max(bits, 1) + 31) // 32
+        e = mag.view(np.uint32).reshape(-1, 2)
+        e = engine.to_device_words(e if ew == 2 else e[:, :1], h.device)
+        neg = c64 < 0
+        sign = torch.from_numpy(neg).to(h.device) if neg.any() else None
+        out, taint = self._pow_rows(h, self.__ct._t, e, sign, max(bits, 1), self.__ct._taint)
+        return PaillierPackedNumber(self.public_key, ipclCipherText(self.public_key.pubkey, out, taint=taint), slot_bits=self.slot_bits,
+                                    slots=self.slots, exponent=self.exponent, value_bits=v, length=G * self.slots)
+
+    def _linear_result(self, out, v: int, we: int, taint: tuple) -> "PaillierPackedNumber":
+        c = ipclCipherText(self.public_key.pubkey, out, taint=taint)
+        return PaillierPackedNumber(self.public_key, c, slot_bits=self.slot_bits, slots=self.slots, exponent=self.exponent + we,
+                                    value_bits=v, length=c.getSize() * self.slots)
+
+    def _composite(self, h, base: torch.Tensor, e: torch.Tensor, sign: torch.Tensor, neg: bool, bits: int, offsets: torch.Tensor):
+        """The defining route of the linear maps: gather the term rows (terms in segment order), raise each to its weight
+        (pai_ct_mul, as scale_rows), multiply the terms of every segment (pai_ct_segment_prod, as segment_sum; an empty segment
+        gives 1).  The headroom was settled by the caller from the exact sums, so the per-step bounds of scale_rows and
+        segment_sum (each looser than the weighted bound) are not applied in between."""
+        PACKED_ROUTES["composite"] += 1
+        terms, taint = self._pow_rows(h, self.__ct._t.index_select(0, base), e, sign.to(torch.bool) if neg else None, bits,
+                                      self.__ct._taint)
+        return h.ct_segment_prod(terms, None, None, offsets), taint
+
+    @staticmethod
+    def _quantized(h, x: torch.Tensor, we: int, bits: int, offsets: Optional[torch.Tensor], what: str):
+        """pai_fp_quantize and its read-back (flag, any w < 0 and the sums in one copy): (e, sign, S = the largest sum of |w|,
+        any w < 0).  `bits` comes from _weight_bits, which has already rejected NaN, infinity and |w| >= 2^126 and is the exact
+        width of the largest |w| — the multi-exponentiation's cost follows it, so it is not replaced by the cap — hence the
+        kernel's flag can only confirm it here; the two branches are the cross-check of the host rounding against the device's."""
+        e, sign, sums, flag = h.fp_quantize(x, we, bits, (bits + 31) // 32, offsets)
+        back = torch.cat([flag.to(torch.int64), sign.any().to(torch.int64).reshape(1), sums.reshape(-1)]).cpu().numpy()
+        if back[0] & 2:
+            raise ValueError(f"{what}: NaN or infinity among the weights")
+        if back[0] & 1:
+            raise OverflowError(f"{what}: a weight does not satisfy |w| < 2^{bits}")
+        pairs = back[2:].view(np.uint64).reshape(-1, 2)
+        S = max(((int(hi) << 64) + int(lo) for lo, hi in pairs), default=0)
+        return e, sign, S, bool(back[1])
+
+    def rmatmul(self, W, *, weight_exponent: int = 0) -> "PaillierPackedNumber":
+        """W @ self for a plaintext dense W of shape (F, G), or (G,) for one output row, G = self.rows (numpy, list, or torch on
+        any device): output row f is prod_i ct_i^(w_fi) mod n^2, so slot j of it holds sum_i w_fi m_(i,j) — with the k residuals of
+        sample i in row i and W = X.T this is the encrypted gradient of all k outputs, one multi-exponentiation per feature.
+        Integer dtypes are taken exactly as w = x << weight_exponent, float dtypes are rounded to w = rint(x 2^weight_exponent)
+        (ties to even); the result has F rows and F * slots elements, the same slot_bits and slots, exponent E + weight_exponent,
+        and value_bits v + bit_length(S), S = max_f sum_i |w_fi| (weighted_sum_value_bits), read from the device before any
+        Paillier kernel runs.  Raises, launching no Paillier kernel: ValueError for a NaN or an infinity, OverflowError for
+        |w| >= 2^126 and when the bound leaves the slot; TypeError / ValueError for dtypes and shapes before anything is launched.
+        Routes with identical bits: pai_fp_quantize, pai_ct_invert when a weight is negative, pai_ct_multiexp; or, below
+        PAI_MEXP_MIN_TERMS weights (the knob of PaillierEncryptedNumber.__matmul__) and for sizes the multi-exponentiation does not
+        serve, term by term (PACKED_ROUTES counts both).  The outputs are canonical products, NOT re-randomised, and carry the
+        input's inversion taint plus the word of an inversion made here: call .apply_obfuscator() on the result before it leaves
+        the party."""
+        we = _weight_exponent(weight_exponent)
+        w = _weights(W, "rmatmul", we)
+        G = self.rows
+        if w.dim() == 1:
+            w = w.reshape(1, -1)
+        if w.dim() != 2 or w.shape[1] != G:
+            raise ValueError(f"rmatmul: weights must have shape (F, {G}) or ({G},), got {tuple(w.shape)}")
+        F = w.shape[0]
+        if G == 0 or F == 0:
+            return self._linear_result(self._no_rows(), self.value_bits, we, self.__ct._taint)
+        h = self.public_key.pubkey.handle
+        w = w.to(h.device)
+        bits = _weight_bits(w, we, "rmatmul")
+        e, sign, S, neg = self._quantized(h, w.t(), we, bits, None, "rmatmul")      # [G, F]: member-major, as pai_ct_multiexp reads
+        v = weighted_sum_value_bits(self.value_bits, S, self.slot_bits)
+        ct, taint = self.__ct._t, self.__ct._taint
+        if F * G >= _mexp_min_terms() and F * G < 1 << 31 and G < 1 << 28:
+            flag = h.new_flag() if neg else None
+            inv = h.ct_invert(ct, flag=flag) if neg else None
+            try:
+                out = h.ct_multiexp(ct, inv, 1, G, F, e.reshape(1, G, F, -1), bits, sign if neg else None)
+            except _native.NativeError as exc:
+                if exc.code != _native.PAI_E_UNSUPPORTED:
+                    raise
+            else:
+                PACKED_ROUTES["fast"] += 1
+                return self._linear_result(out, v, we, merge_taint(taint, (flag,)) if neg else taint)
+        # terms in output order: term f G + i is row i raised to w_fi
+        dev = h.device
+        base = torch.arange(G, device=dev).repeat(F)
+        offsets = torch.arange(F + 1, device=dev, dtype=torch.int64) * G
+        out, taint = self._composite(h, base, e.permute(1, 0, 2).reshape(F * G, -1).contiguous(), sign.t().reshape(-1), neg, bits, offsets)
+        return self._linear_result(out, v, we, taint)
+
+    def csr_rmatmul(self, indptr, indices, data, shape, *, weight_exponent: int = 0) -> "PaillierPackedNumber":
+        """A @ self for a plaintext sparse A of shape (m, G), G = self.rows, given as CSR arrays (numpy, or torch on any device; no
+        scipy needed) under the argument rules and errors of PaillierEncryptedNumber.csr_rmatmul: output row i is the product of
+        ct_l^(w) over the STORED entries (i, l) — explicit zeros and duplicates count as terms, a row of A without stored entries
+        gives the ciphertext 1 (all slots 0).  Weights, exponent, headroom (S = the largest per-row sum of |w|, from the device),
+        errors and taint as for rmatmul; the fast route is pai_ct_sparse_multiexp on the CSR arrays as they are (d_base = indices,
+        d_offsets = indptr), the term-by-term route is taken below PAI_MEXP_MIN_TERMS stored entries.  NOT re-randomised (a row
+        without entries is recognisable as 1): call .apply_obfuscator() on the result before it leaves the party."""
+        we = _weight_exponent(weight_exponent)
+        G = self.rows
+        ptr, idx, d, (m, n, k) = _csr_args(indptr, indices, data, shape, G, True)
+        if k != 1:
+            raise ValueError(f"csr_rmatmul: the matrix must have {G} columns (one per row of the container), got {n}")
+        w = _weights(d, "csr_rmatmul", we)
+        h = self.public_key.pubkey.handle
+        dev = h.device
+        w, offsets, base = w.to(dev), ptr.to(dev), idx.to(dev)
+        T = w.shape[0]
+        if T == 0:                                       # no stored entry: every row is the ciphertext 1
+            one = h.raw_encrypt(torch.zeros((m, h.n_words), dtype=torch.int32, device=dev))
+            return self._linear_result(one, self.value_bits, we, self.__ct._taint)
+        bits = _weight_bits(w, we, "csr_rmatmul")
+        e, sign, S, neg = self._quantized(h, w, we, bits, offsets, "csr_rmatmul")
+        v = weighted_sum_value_bits(self.value_bits, S, self.slot_bits)
+        ct, taint = self.__ct._t, self.__ct._taint
+        if T >= _mexp_min_terms() and T < 1 << 31 and G < 1 << 28:
+            flag = h.new_flag() if neg else None
+            inv = h.ct_invert(ct, flag=flag) if neg else None
+            try:
+                out = h.ct_sparse_multiexp(ct, inv, base.to(torch.int32), e, bits, sign if neg else None, offsets)
+            except _native.NativeError as exc:
+                if exc.code != _native.PAI_E_UNSUPPORTED:
+                    raise
+            else:
+                PACKED_ROUTES["fast"] += 1
+                return self._linear_result(out, v, we, merge_taint(taint, (flag,)) if neg else taint)
+        out, taint = self._composite(h, base, e, sign, neg, bits, offsets)
+        return self._linear_result(out, v, we, taint)
+
+    def __rmatmul__(self, other):
+        """W @ packed: rmatmul for a dense W (weight_exponent 0), csr_rmatmul for a scipy sparse one."""
+        sp = _scipy_sparse(other)
+        if sp is not None:
+            return self.csr_rmatmul(sp.indptr, sp.indices, sp.data, sp.shape)
+        return self.rmatmul(other)
+
+    def __matmul__(self, other):
+        raise TypeError("PaillierPackedNumber @ W is not defined: a matrix on the right would have to split rows (the slots of a "
+                        "ciphertext), which no operation on ciphertexts does; W @ packed combines whole rows")
