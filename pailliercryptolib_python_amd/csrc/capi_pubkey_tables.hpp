@@ -286,7 +286,7 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
         if (v >= 2 && (v & (v - 1)) == 0 && (size_t)v <= ((size_t)1 << dwb)) K = (int)v;
     }
     const int tw = pk->n_words;
-    if ((tw + 63) / 64 > 4) return;                                      // inv_eea instantiations: up to 256 words
+    if ((tw + 63) / 64 > 4) return;                                      // the totals are n_words wide: at most 4 words per lane of k_inv_eea_wave (inv_eea.hip serves up to 5)
     const size_t slab_max = (size_t)1 << 22;                             // entries per slab: 1.2 GB of prefix scratch at 72 limbs
     const size_t slab = std::min(NE, slab_max) / K * K;
     ScopedDevBuf d_pref, d_tot, d_inv, d_fail;

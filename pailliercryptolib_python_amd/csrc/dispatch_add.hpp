@@ -17,7 +17,7 @@ int pai_ct_add(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, i
         const bool msb = L == nullptr && pk->d_msb != nullptr && !b_bcast && !knob_disabled("add_msb");
         if (msb) {
             const GeoOps* g = pk->msq.geo;
-            ScopedKernelTimer t("k_modmul_msb", (hipStream_t)stream);
+            ScopedKernelTimer t("k_modmul_msb", (hipStream_t)stream, "lane_group");
             g->modmul_msb((hipStream_t)stream, grid_for(g, N, pk->dev.ncu), pk->d_msb, d_a, d_b, d_out, (int)N, pk->ct_words);
             t.stop();
             HIP_CHECK(hipGetLastError());
@@ -26,7 +26,7 @@ int pai_ct_add(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, i
         const GeoOps* g = L ? L->geo : pk->msq.geo;
         // small batches without a broadcast addend: the two products on the minus-one context of n^2 (PAI_DISABLE=lat_add_m1)
         const bool m1 = L != nullptr && !b_bcast && pk->lat_m1_ok && g->t >= 16 && !knob_disabled("lat_add_m1");
-        ScopedKernelTimer t("k_modmul", (hipStream_t)stream);
+        ScopedKernelTimer t("k_modmul", (hipStream_t)stream, L ? (m1 ? "lat_m1" : "lat") : "lane_group");
         g->modmul((hipStream_t)stream, L ? (int)((N + g->epb - 1) / g->epb) : grid_for(g, N, pk->dev.ncu),
                   m1 ? pk->lat_msq_m1.d_ctx : (L ? L->d_ctx : pk->msq.d_ctx), d_a, d_b, d_out, (int)N, pk->ct_words, b_bcast,
                   MODMUL_FULL, m1 ? pk->lat_msq.d_ctx : nullptr);
@@ -47,7 +47,7 @@ static void add_aligned_common(const pai_pubkey* pk, const uint32_t* d_a, const 
     // ... on the minus-one context of n^2 where the key has one (PAI_DISABLE=lat_add_m1: the conventional context)
     const bool m1 = L != nullptr && pk->lat_m1_ok && g->t >= 16 && !knob_disabled("lat_add_m1");
     g_last_times.clear();
-    ScopedKernelTimer t("k_add_aligned", (hipStream_t)stream);
+    ScopedKernelTimer t("k_add_aligned", (hipStream_t)stream, L ? (m1 ? "lat_m1" : "lat") : "lane_group");
     g->add_aligned((hipStream_t)stream, L ? (int)((N + g->epb - 1) / g->epb) : grid_for(g, N, pk->dev.ncu),
                    m1 ? pk->lat_msq_m1.d_ctx : (L ? L->d_ctx : pk->msq.d_ctx), d_a, d_b, b_bcast, d_delta, d_out, (int)N,
                    pk->ct_words, d_entry, m1 ? pk->lat_msq.d_ctx : nullptr);
@@ -91,7 +91,7 @@ int pai_ct_mont_mul(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d
         g_last_times.clear();
         if (const ModSetup* L = lat_add_ctx(pk, N, true)) {
             const GeoOps* gl = L->geo;
-            ScopedKernelTimer t("k_modmul", (hipStream_t)stream);
+            ScopedKernelTimer t("k_modmul", (hipStream_t)stream, "lat");
             gl->modmul((hipStream_t)stream, (int)((N + gl->epb - 1) / gl->epb), L->d_ctx, d_a, d_b, d_out, (int)N, pk->ct_words, b_bcast,
                        MODMUL_FULL, nullptr);
             t.stop();
@@ -99,7 +99,7 @@ int pai_ct_mont_mul(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d
             return;
         }
         const GeoOps* g = pk->msq.geo;
-        ScopedKernelTimer t("k_modmul", (hipStream_t)stream);
+        ScopedKernelTimer t("k_modmul", (hipStream_t)stream, "lane_group");
         g->modmul((hipStream_t)stream, grid_for(g, N, pk->dev.ncu), pk->msq.d_ctx, d_a, d_b, d_out, (int)N, pk->ct_words, b_bcast,
                   MODMUL_MONT, nullptr);
         t.stop();

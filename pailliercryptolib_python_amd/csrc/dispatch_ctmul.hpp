@@ -24,7 +24,7 @@ static void ctmul_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32
     Q.ebits_max = ebits_max;
     Q.e_bcast = e_bcast;
     OrderScope order_5(pk->order, s);
-    ScopedKernelTimer t(timer_name, s);
+    ScopedKernelTimer t(timer_name, s, "padic");
     if (!launch_ctmul_padic(pk->penc_nl, s, grid, Q, d_ct, d_e, d_out, (int)N))
         throw PaiError(PAI_E_INTERNAL, "no digit-engine ct*pt kernel for this limb count");
     t.stop();
@@ -35,7 +35,7 @@ static void ctmul_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32
 // ct^e on lane-group digit pairs (k_pair_ctmul, then w + v n on the n^2 geometry: k_pair_finish); the caller holds pk->mu
 static void ctmul_pair_locked(const pai_pubkey* pk, hipStream_t s, int nl, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* kdig,
                               const uint32_t* one, int nd, int out_words, const uint32_t* d_ct, const uint32_t* d_e, int e_words,
-                              int ebits_max, int e_bcast, size_t N, uint32_t* d_out) {
+                              int ebits_max, int e_bcast, size_t N, uint32_t* d_out, const char* path) {
     const GeoOps* g = pk->msq.geo;
     const int grid = grid_for(g, N, pk->dev.ncu);
     const int wbits = var_window_bits(ebits_max);
@@ -67,7 +67,7 @@ static void ctmul_pair_locked(const pai_pubkey* pk, hipStream_t s, int nl, const
     P.ct_words = pk->ct_words;
     P.r_words = pk->r_words;
     OrderScope order_(pk->order, s);
-    ScopedKernelTimer t("k_ctmul", s);
+    ScopedKernelTimer t("k_ctmul", s, path);
     if (!launch_pair_ctmul(nl, s, pgrid, Q, d_ct, d_e, pk->pair_wv.as<uint32_t>(), (int)N))
         throw PaiError(PAI_E_INTERNAL, "no digit-pair ct * pt kernel for this limb count");
     g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), out_words, nullptr, d_out, (int)N, 0);
@@ -120,7 +120,7 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
             std::lock_guard<std::mutex> lk(pk->mu);
             if (ensure_midp(pk)) {
                 ctmul_pair_locked(pk, s, pk->midp_nl, pk->midp_n.d_ctx, pk->d_midp_nm1, pk->d_midp_kdig, pk->d_midp_one, pk->midp_nd,
-                                  pk->midp_out_words, d_ct, d_e, e_words, ebits_max, e_bcast, N, d_out);
+                                  pk->midp_out_words, d_ct, d_e, e_words, ebits_max, e_bcast, N, d_out, "pair4");
                 return;
             }
         }
@@ -145,7 +145,7 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
                 Q.e_words = e_words;
                 Q.e_bcast = e_bcast;
                 OrderScope order_6(pk->order, s);
-                ScopedKernelTimer t("k_ctmul", s);
+                ScopedKernelTimer t("k_ctmul", s, "pp");
                 launch_ctmul_pp(s, (int)N, Q, d_ct, d_out, pk->lat_pp_chain);
                 t.stop();
                 HIP_CHECK(hipGetLastError());
@@ -162,7 +162,7 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
                 const int wbits = rl ? 0 : var_window_bits(ebits_max);
                 if (!rl) pk->lat_table.ensure(((size_t)1 << wbits) * g->nl * (size_t)grid * g->epb * 4);
                 OrderScope order_7(pk->order, s);
-                ScopedKernelTimer t("k_ctmul", s);
+                ScopedKernelTimer t("k_ctmul", s, rl ? "rl" : "window");
                 g->modexp_var_win(s, grid, pk->lat_m1_ok ? pk->lat_msq_m1.d_ctx : pk->lat_msq.d_ctx, d_ct, pk->ct_words, d_e, e_words,
                                   ebits_max, e_bcast, d_out, pk->ct_words, (int)N, pk->lat_table.as<uint32_t>(), wbits,
                                   pk->lat_m1_ok ? pk->lat_msq.d_ctx : nullptr);
@@ -186,7 +186,7 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
             // pairs (k_pair_ctmul) instead of 8 NL^2 per Montgomery product modulo n^2, then w + v n (k_pair_finish)
             std::lock_guard<std::mutex> lk(pk->mu);
             ctmul_pair_locked(pk, s, pk->pair_nl, pk->npair.d_ctx, pk->d_pair_nm1, pk->d_pair_kdig, pk->d_pair_one, pk->pair_nd,
-                              pk->pair_out_words, d_ct, d_e, e_words, ebits_max, e_bcast, N, d_out);
+                              pk->pair_out_words, d_ct, d_e, e_words, ebits_max, e_bcast, N, d_out, "pair");
             return;
         }
         if (ebits_max > 8) {
@@ -194,7 +194,7 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
             const int wbits = var_window_bits(ebits_max);
             pk->ctmul_table.ensure(((size_t)1 << wbits) * g->nl * (size_t)grid * g->epb * 4);
             OrderScope order_8(pk->order, s);
-            ScopedKernelTimer t("k_ctmul", s);
+            ScopedKernelTimer t("k_ctmul", s, "lane_group");
             g->modexp_var_win(s, grid, pk->msq.d_ctx, d_ct, pk->ct_words, d_e, e_words, ebits_max, e_bcast, d_out,
                               pk->ct_words, (int)N, pk->ctmul_table.as<uint32_t>(), wbits, nullptr);
             t.stop();
@@ -286,8 +286,9 @@ static int ct_pow2_impl(const pai_pubkey* pk, uint32_t* d_ct, const int32_t* d_d
             }
             if (dmax == 0) return;
         }
-        ScopedKernelTimer t("k_pow2", (hipStream_t)stream);
-        if (const ModSetup* L = lat_add_ctx(pk, N, false, 4)) {           // small batches: an integer per wavefront (as the aligned additions)
+        const ModSetup* L = lat_add_ctx(pk, N, false, 4);
+        ScopedKernelTimer t("k_pow2", (hipStream_t)stream, L ? "lat" : "lane_group");
+        if (L) {           // small batches: an integer per wavefront (as the aligned additions)
             const GeoOps* gl = L->geo;
             const bool m1 = pk->lat_m1_ok && gl->t >= 16 && !knob_disabled("lat_add_m1");       // ... on the minus-one context of n^2
             gl->pow2((hipStream_t)stream, (int)((N + gl->epb - 1) / gl->epb), m1 ? pk->lat_msq_m1.d_ctx : L->d_ctx, d_ct, d_delta, delta_bcast,

@@ -294,7 +294,7 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
             Q.e_bcast = 1;
             Q.out_words = M.out_words;
             {
-                ScopedKernelTimer t("k_dec_a", s);
+                ScopedKernelTimer t("k_dec_a", s, "pair4");
                 if (!launch_pair_ctmul(M.nl, s, pgrid, Q, d_ct, sk->d_expo[0], M.wv[0].as<uint32_t>(), (int)N))
                     throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this prime size");
                 for (int w = 0; w < 2; ++w) {
@@ -393,11 +393,11 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
                     Q.nch = L.pp_nch;
                     Q.ct_words = pk->ct_words;
                     Q.u_words = u_words;
-                    ScopedKernelTimer t("k_dec_a", s);
+                    ScopedKernelTimer t("k_dec_a", s, "pp");
                     launch_dec_a_pp(s, (int)N, Q, d_ct, sk->ubuf.as<uint32_t>(), L.pp_chain);
                     t.stop();
                 } else {
-                    ScopedKernelTimer t("k_dec_a", s);
+                    ScopedKernelTimer t("k_dec_a", s, rl ? "rl" : (dense ? "window_dense" : "window"));
                     ga->dec_a(s, gridx, A, d_ct, sk->ubuf.as<uint32_t>(), (int)N, L.table.as<uint32_t>());
                     t.stop();
                 }
@@ -445,7 +445,11 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
         A.u_words = sk->u_words;
         g_last_times.clear();
         {
-            ScopedKernelTimer t("k_dec_a", s);
+            const bool sqr_kara = !knob_disabled("padic_kara");      // PAI_DISABLE=padic_kara: the row-wise squaring
+            const bool mul_kara = !knob_disabled("padic_kara_mul");  // PAI_DISABLE=padic_kara_mul: row-wise products, LDS hand-over
+            // (36 limbs: squarings and products by Karatsuba columns unless PAI_DISABLE says otherwise; the other limb counts row-wise)
+            const char* padic_path = sk->padic_nl != 36 ? "padic" : (!sqr_kara ? "padic_rowwise" : (mul_kara ? "padic_kara_mul" : "padic_kara"));
+            ScopedKernelTimer t("k_dec_a", s, sk->padic_nl ? padic_path : (sk->wide_nl ? "wide" : "lane_group"));
             if (sk->padic_nl) {
                 DecPadicParams Q;
                 for (int w = 0; w < 2; ++w) {
@@ -460,8 +464,8 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
                 Q.wscratch = sk->wscratch.as<uint4>();
                 Q.ct_words = pk->ct_words;
                 Q.u_words = sk->u_words;
-                Q.sqr_kara = !knob_disabled("padic_kara");      // PAI_DISABLE=padic_kara: the row-wise squaring
-                Q.mul_kara = !knob_disabled("padic_kara_mul");  // PAI_DISABLE=padic_kara_mul: row-wise products, LDS hand-over
+                Q.sqr_kara = sqr_kara;
+                Q.mul_kara = mul_kara;
                 if (!launch_dec_a_padic(sk->padic_nl, s, gridx, Q, d_ct, sk->ubuf.as<uint32_t>(), (int)N, sk->table.as<uint32_t>()))
                     throw PaiError(PAI_E_INTERNAL, "no p-adic kernel for this limb count");
             } else if (sk->wide_nl) {

@@ -36,7 +36,7 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             const size_t tiles = (N + epb - 1) / epb;
             const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu * 8));
             OrderScope order_2(pk->order, s);
-            ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s);
+            ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s, "pair4");
             if (!launch_pair_fixed_base(pk->midp_nl, s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0))
                 throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this limb count");
             g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), pk->midp_out_words, d_ct_in, d_ct_out, (int)N, from_plain ? 0 : 1);
@@ -120,7 +120,7 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             PL.ct_words = pk->ct_words;
             PL.r_words = pk->r_words;
             OrderScope order_3(pk->order, s);
-            ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s);
+            ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s, m1 ? "lat_tree_m1" : (tree ? "lat_tree" : "lat_chain"));
             const int per_wg = tree ? 64 / gl->t : gl->epb;
             gl->encrypt(s, (int)((N + per_wg - 1) / per_wg), PL, d_m, d_r, d_ct_in, d_ct_out, (int)N, (from_plain ? 1 : 2) + (tree ? 4 : 0));
             t.stop();
@@ -147,7 +147,7 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         PL.pt_words = pk->n_words;
         PL.ct_words = pk->ct_words;
         PL.r_words = pk->r_words;
-        ScopedKernelTimer t("k_encrypt(raw)", s);
+        ScopedKernelTimer t("k_encrypt(raw)", s, "lat");
         gl->encrypt(s, (int)((N + gl->epb - 1) / gl->epb), PL, d_m, nullptr, nullptr, d_ct_out, (int)N, 0);
         t.stop();
         HIP_CHECK(hipGetLastError());
@@ -174,7 +174,7 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         Q.r_words = pk->r_words;
         const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
-        ScopedKernelTimer t(!from_plain ? "k_encrypt(obfuscate)" : (d_r ? "k_encrypt(djn)" : "k_encrypt(raw)"), s);
+        ScopedKernelTimer t(!from_plain ? "k_encrypt(obfuscate)" : (d_r ? "k_encrypt(djn)" : "k_encrypt(raw)"), s, "padic");
         if (!launch_encrypt_padic(pk->penc_nl, s, pgrid, Q, d_m, d_r, d_ct_in, d_ct_out, (int)N, !from_plain ? 2 : (d_r ? 1 : 0)))
             throw PaiError(PAI_E_INTERNAL, "no digit-engine encrypt kernel for this limb count");
         t.stop();
@@ -195,18 +195,18 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         const int epb = pair_epb(pk->pair_nl);
         const size_t tiles = (N + epb - 1) / epb;
         const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu * 2));
-        ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s);
+        ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s, "pair");
         if (!launch_pair_fixed_base(pk->pair_nl, s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0))
             throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this limb count");
         g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), pk->pair_out_words, d_ct_in, d_ct_out, (int)N, from_plain ? 0 : 1);
         t.stop();
     } else if (d_r == nullptr) {
         require(from_plain, "obfuscation needs randomness");
-        ScopedKernelTimer t("k_encrypt(raw)", s);
+        ScopedKernelTimer t("k_encrypt(raw)", s, "lane_group");
         g->encrypt(s, grid, P, d_m, nullptr, nullptr, d_ct_out, (int)N, 0);
         t.stop();
     } else if (pk->djn) {
-        ScopedKernelTimer t("k_encrypt(djn)", s);
+        ScopedKernelTimer t("k_encrypt(djn)", s, "lane_group");
         g->encrypt(s, grid, P, d_m, d_r, d_ct_in, d_ct_out, (int)N, from_plain ? 1 : 2);
         t.stop();
     } else {
@@ -228,7 +228,7 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             Q.table = pk->table.as<uint4>();
             Q.in_words = pk->n_words;
             Q.ct_words = pk->ct_words;
-            ScopedKernelTimer t("k_pow(r^n)", s);
+            ScopedKernelTimer t("k_pow(r^n)", s, "padic");
             if (!launch_pow_padic(pk->penc_nl, s, pgrid, Q, d_r, pk->tmp.as<uint32_t>(), (int)N))
                 throw PaiError(PAI_E_INTERNAL, "no digit-engine power kernel for this limb count");
             t.stop();

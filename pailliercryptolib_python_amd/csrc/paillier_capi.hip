@@ -332,16 +332,18 @@ static MsbCtx* build_msb_ctx(const Limbs& M, const GeoOps* g, int w32) {
 }
 
 // Optional per-kernel timing with HIP events on the caller's stream (pai_profile_enable): used by
-// bench.py to report the dominant kernel's duration next to the rocprofv3 numbers.
+// bench.py to report the dominant kernel's duration next to the rocprofv3 numbers.  `path` names the kernel family the dispatcher
+// chose where one name covers several (pai_profile_last_path: the tests' proof that a forced family ran).
 bool g_profile = false;
-struct KernelTime { std::string name; float ms; };
+struct KernelTime { std::string name; float ms; const char* path; };
 thread_local std::vector<KernelTime> g_last_times;
 struct ScopedKernelTimer {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipStream_t s;
     const char* name;
+    const char* path;
     bool on;
-    ScopedKernelTimer(const char* n, hipStream_t st) : s(st), name(n), on(g_profile) {
+    ScopedKernelTimer(const char* n, hipStream_t st, const char* p = "") : s(st), name(n), path(p), on(g_profile) {
         if (!on) return;
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
@@ -353,7 +355,7 @@ struct ScopedKernelTimer {
         HIP_CHECK(hipEventSynchronize(e1));
         float ms = 0.f;
         HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        g_last_times.push_back({name, ms});
+        g_last_times.push_back({name, ms, path});
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         e0 = e1 = nullptr;
@@ -713,6 +715,12 @@ int pai_profile_last(int index, char* name_out, size_t name_cap, float* ms_out) 
         name_out[name_cap - 1] = 0;
     }
     if (ms_out) *ms_out = g_last_times[index].ms;
+    return PAI_OK;
+}
+int pai_profile_last_path(int index, char* path_out, size_t path_cap) {
+    if (index < 0 || (size_t)index >= g_last_times.size() || !path_out || !path_cap) return PAI_E_INVALID;
+    std::strncpy(path_out, g_last_times[index].path, path_cap - 1);
+    path_out[path_cap - 1] = 0;
     return PAI_OK;
 }
 

@@ -2,7 +2,8 @@
 columns (csrc/mont_padic.hpp: sqr_kara, the default) and by the row-wise form (PAI_DISABLE=padic_kara), against the
 Python-int oracle at a 2048-bit key: ciphertexts whose residues modulo p^2 and q^2 sit at the extremes (1, s^2 - 1, s + 1,
 ...) next to random ones, in batches that are not a multiple of the 256-element tile.  The cell bounds of the squaring are
-held by tests/test_padic_kara_cpu.py."""
+held by tests/test_padic_kara_cpu.py.  Structured primes (limbs all ones / all zero, halves at opposite extremes):
+tests/test_gpu_extreme_keys.py."""
 import random
 
 import pytest

@@ -4,7 +4,8 @@ the products row-wise (PAI_DISABLE=padic_kara_mul) and with everything row-wise 
 Python-int oracle at a 2048-bit key: ciphertexts whose residues modulo p^2 and q^2 sit at the extremes (1, s^2 - 1, s + 1,
 ...) next to random ones, in batches that are not a multiple of the 256-element tile.  One more key has primes whose
 s - 1 is mostly zero bits: long runs of squarings between few products, and windows that are a single bit.  The cell
-bounds of the product are held by tests/test_padic_kara_mul_cpu.py."""
+bounds of the product are held by tests/test_padic_kara_mul_cpu.py.  Structured primes (limbs all ones / all zero, halves at
+opposite extremes, n0inv = 1 / 2^29 - 1) on all three modes: tests/test_gpu_extreme_keys.py."""
 import random
 
 import pytest

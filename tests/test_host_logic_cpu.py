@@ -71,12 +71,18 @@ def test_msb_first_product_model_bounds():
     import random
     from pathlib import Path
 
+    from tests.test_extreme_keys_cpu import load_extreme_keys
+
     spec = importlib.util.spec_from_file_location("msb_model", Path(__file__).resolve().parent.parent / "tools" / "msb_model.py")
     mm = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mm)
     rng = random.Random(5)
     for key, (NLL, T, U) in mm.GEOS.items():
-        for M in (mm.rand_modulus(2 * key, rng), (1 << (2 * key)) - 1 - 2 * rng.getrandbits(40), (1 << (2 * key - 1)) + 1 + 2 * rng.getrandbits(40)):
+        # ... and n^2 of the structured keys of tests/golden/extreme_keys.json: all-ones and all-zero limbs, n = -1 and n = 1 modulo 2^58
+        # (n^2 of the `zeros` keys is one bit short of 2 key bits)
+        extreme = [(p_ * q_) ** 2 for _, f, b, p_, q_ in load_extreme_keys() if 2 * b == key and f in ("ones", "zeros", "n0", "n0_one")]
+        assert len(extreme) == 4
+        for M in [mm.rand_modulus(2 * key, rng), (1 << (2 * key)) - 1 - 2 * rng.getrandbits(40), (1 << (2 * key - 1)) + 1 + 2 * rng.getrandbits(40)] + extreme:
             p = mm.Params(M, NLL, T, U)
             assert p.ok
             full = (1 << (2 * key)) - 1

@@ -41,3 +41,25 @@ def test_kara_squaring_model_extreme_limbs():
     w, v = km.sqr_kara(top, top, p, NL, st)
     x = (top + top * p) % (p * p)
     assert (w + v * p) % (p * p) == pow(x, 2, p * p) * pow(R, -1, p * p) % (p * p)
+
+
+def test_kara_squaring_model_extreme_primes():
+    """The same corners with the modulus at the extremes (tests/golden/extreme_keys.json: limbs all ones, all zero, low half ones /
+    high half zero, = 1 and = -1 modulo 2^58) on 36 limbs (1024-bit primes) and 24 limbs (512 bits, and 676 bits: the widest prime
+    the geometry admits, R / p = 2^20 exactly); a run of squarings stays inside the lazy bound."""
+    import random
+
+    from tests.test_extreme_keys_cpu import load_extreme_keys
+
+    km = _model()
+    rng = random.Random(3)
+    st = km.Stats()
+    for bits, NL in ((1024, 36), (512, 24), (676, 24)):
+        for p in sorted({v for _, _, b, p_, q_ in load_extreme_keys() if b == bits for v in (p_, q_)}):
+            for a, b, ok in km.corners(p, NL, rng):
+                km.sqr_kara(a, b, p, NL, st, in_range=ok)
+            a, b = 2 * p - 1, 2 * p - 1
+            for _ in range(4):
+                a, b = km.sqr_kara(a, b, p, NL, st)
+                assert a < 2 * p + (p >> 18) and b < 2 * p + (p >> 18)
+    assert st.max_col < 1 << 64 and st.max_cc < 1 << 64 and st.max_d < 1 << 64

@@ -11,6 +11,16 @@ from pathlib import Path
 NL = 36
 
 
+def extreme_primes(bits):
+    """The structured primes of tests/golden/extreme_keys.json at one width: limbs all ones, all zero, low half ones / high half zero,
+    and = 1 / = -1 modulo 2^58 (quotient digits t * n0inv with n0inv = 2^29 - 1 / 1)."""
+    from tests.test_extreme_keys_cpu import load_extreme_keys
+
+    out = sorted({v for _, _, b, p, q in load_extreme_keys() if b == bits for v in (p, q)})
+    assert len(out) == 8
+    return out
+
+
 def _model():
     spec = importlib.util.spec_from_file_location("kara_model", Path(__file__).resolve().parent.parent / "tools" / "kara_model.py")
     km = importlib.util.module_from_spec(spec)
@@ -48,8 +58,7 @@ def test_kara_product_all_ones_limbs():
 def test_kara_product_lazy_bound():
     km = _model()
     rng = random.Random(6)
-    for bits in (1024, 1000):
-        p = km.random_prime(bits, rng)
+    for p in [km.random_prime(bits, rng) for bits in (1024, 1000)] + extreme_primes(1024):
         top = 2 * p + (p >> 18) - 1
         st = km.Stats()
         for a, b, c, d in ((top, top, top, top), (top, 0, 0, top), (0, top, top, 0), (top, top, 1, 0), (p - 1, p - 1, p - 1, p - 1)):
@@ -74,6 +83,10 @@ def test_kara_product_opposite_sign_differences():
                 for d in (hi_lo, lo_hi):
                     got = km.mul_kara(a, b, c, d, p, NL, st, in_range=False)
                     assert got == _rowwise(km, a, b, c, d, p)
+    # ... and with the modulus itself at those extremes (one operand of every reduction column is p)
+    for p in extreme_primes(1024):
+        for a, b, c, d in ((lo_hi, hi_lo, hi_lo, lo_hi), (hi_lo, lo_hi, alt, full - alt), (full, full, full, full)):
+            assert km.mul_kara(a, b, c, d, p, NL, st, in_range=False) == _rowwise(km, a, b, c, d, p)
     assert st.max_cc < 1 << 64 and st.max_d < 1 << 64
 
 
@@ -81,8 +94,7 @@ def test_kara_product_random_pairs():
     km = _model()
     rng = random.Random(8)
     st = km.Stats()
-    for bits in (1024, 1000):
-        p = km.random_prime(bits, rng)
+    for p in [km.random_prime(bits, rng) for bits in (1024, 1000)] + extreme_primes(1024):
         top = 2 * p + (p >> 18)
         for _ in range(12):
             a, b, c, d = (rng.randrange(top) for _ in range(4))
