@@ -84,6 +84,8 @@ static bool ensure_lat_ctx(const pai_pubkey* pk);
 // per window) and the full table (one product per entry) are computed on the device.
 void build_pair_fb(pai_pubkey* pk, int wb, int J) {
     const int nl = pk->pair_nl;
+    const auto fb_chain = launcher(pair_ops(nl), &PairOps::fb_chain, "no digit-pair table kernel for this limb count");
+    const auto fb_expand = launcher(pair_ops(nl), &PairOps::fb_expand, "no digit-pair table kernel for this limb count");
     const bool two_level = (wb % 2 == 0) && wb >= 8;
     const int h = two_level ? wb / 2 : wb;
     const int J1 = two_level ? 2 * J : J;
@@ -132,12 +134,11 @@ void build_pair_fb(pai_pubkey* pk, int wb, int J) {
         fbb.kdig = pk->d_pair_kdig;
         fbb.nd = pk->pair_nd;
     }
-    bool ok = launch_pair_fb_chain(nl, nullptr, g1, pk->npair.d_ctx, pk->d_pair_nm1, d_bases.as<uint32_t>(), d_one.as<uint32_t>(),
-                                   level1, J1, h, fbb);
+    fb_chain(nullptr, g1, pk->npair.d_ctx, pk->d_pair_nm1, d_bases.as<uint32_t>(), d_one.as<uint32_t>(), level1, J1, h, fbb);
     hipError_t e1 = hipGetLastError();
-    if (ok && two_level && e1 == hipSuccess) {
+    if (two_level && e1 == hipSuccess) {
         const int g2 = (int)std::max<size_t>(1, std::min<size_t>((NE + epb - 1) / epb, (size_t)pk->dev.ncu * 2));
-        ok = launch_pair_fb_expand(nl, nullptr, g2, pk->npair.d_ctx, pk->d_pair_nm1, level1, pk->d_pair_fb, J, h);
+        fb_expand(nullptr, g2, pk->npair.d_ctx, pk->d_pair_nm1, level1, pk->d_pair_fb, J, h);
         e1 = hipGetLastError();
     }
     hipError_t e2 = hipDeviceSynchronize();
@@ -146,11 +147,10 @@ void build_pair_fb(pai_pubkey* pk, int wb, int J) {
     d_half.release();
     d_plain.release();
     d_hs_plain.release();
-    if (!ok || e1 != hipSuccess || e2 != hipSuccess) {
+    if (e1 != hipSuccess || e2 != hipSuccess) {
         (void)hipFree(pk->d_pair_fb);
         pk->d_pair_fb = nullptr;
     }
-    if (!ok) throw PaiError(PAI_E_INTERNAL, "no digit-pair table kernel for this limb count");
     HIP_CHECK(e1);
     HIP_CHECK(e2);
     pk->pair_windows = J;
@@ -279,6 +279,8 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
     if (knob_disabled("gform")) return;
     if (!padic_enc_gform_supported()) return;
     const int pnl = pk->penc_nl;
+    const auto g_prefix = launcher(padic_enc_ops(pnl), &PadicEncOps::g_prefix, "no g-factoring kernel for this limb count");
+    const auto g_finish = launcher(padic_enc_ops(pnl), &PadicEncOps::g_finish, "no g-factoring kernel for this limb count");
     // chunk length: divides the entries of a window, hence NE; one extended GCD per K entries.  64 measured best (first 2^20
     // encryption of a 2048-bit key 0.188 s; 256-entry chunks measured slower)
     int K = (int)std::min<size_t>(64, (size_t)1 << dwb);
@@ -308,9 +310,7 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
     for (size_t e0 = 0; e0 < NE; e0 += slab) {
         const size_t cnt = std::min(slab, NE - e0);
         uint32_t* tbl = pk->d_fb_dig + e0 * ent_words;
-        if (!launch_fb_g_prefix_padic(pnl, nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw,
-                                      pk->d_mscratch))
-            throw PaiError(PAI_E_INTERNAL, "no g-factoring kernel for this limb count");
+        g_prefix(nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw, pk->d_mscratch);
         HIP_CHECK(hipGetLastError());
         if (!launch_inv_eea(nullptr, tw, pk->d_nexp, d_tot.as<uint32_t>(), d_inv.as<uint32_t>(), (int)(cnt / K), 2 * 32 * tw + 64,
                             d_fail.as<int>()))
@@ -319,8 +319,7 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
         int fail = 0;
         HIP_CHECK(hipMemcpy(&fail, d_fail.p, 4, hipMemcpyDeviceToHost));
         if (fail) throw PaiError(PAI_E_INTERNAL, "fixed-base table entry without an inverse modulo n");
-        launch_fb_g_finish_padic(pnl, nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw,
-                                 pk->d_mscratch);
+        g_finish(nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw, pk->d_mscratch);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipDeviceSynchronize());
@@ -331,6 +330,8 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
 static void gfactor_pair_table(pai_pubkey* pk, size_t NE, int wb) {
     if (knob_disabled("gform")) return;
     const int nl = pk->pair_nl;
+    const auto g_prefix = launcher(pair_ops(nl), &PairOps::g_prefix, "no g-factoring kernel for this limb count");
+    const auto g_finish = launcher(pair_ops(nl), &PairOps::g_finish, "no g-factoring kernel for this limb count");
     const int K = (int)std::min<size_t>(64, (size_t)1 << wb);
     const int tw = pk->n_words;
     if ((tw + 63) / 64 > 4) return;
@@ -352,8 +353,7 @@ static void gfactor_pair_table(pai_pubkey* pk, size_t NE, int wb) {
         const size_t cnt = std::min(slab, NE - e0);
         uint32_t* tbl = pk->d_pair_fb + e0 * ent_words;
         const int grid = (int)std::max<size_t>(1, std::min<size_t>((cnt / K + epb - 1) / epb, (size_t)pk->dev.ncu * 2));
-        if (!launch_pair_g_prefix(nl, nullptr, grid, pk->npair.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw))
-            throw PaiError(PAI_E_INTERNAL, "no g-factoring kernel for this limb count");
+        g_prefix(nullptr, grid, pk->npair.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw);
         HIP_CHECK(hipGetLastError());
         if (!launch_inv_eea(nullptr, tw, pk->d_nexp, d_tot.as<uint32_t>(), d_inv.as<uint32_t>(), (int)(cnt / K), 2 * 32 * tw + 64,
                             d_fail.as<int>()))
@@ -362,7 +362,7 @@ static void gfactor_pair_table(pai_pubkey* pk, size_t NE, int wb) {
         int fail = 0;
         HIP_CHECK(hipMemcpy(&fail, d_fail.p, 4, hipMemcpyDeviceToHost));
         if (fail) throw PaiError(PAI_E_INTERNAL, "fixed-base table entry without an inverse modulo n");
-        launch_pair_g_finish(nl, nullptr, grid, pk->npair.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw);
+        g_finish(nullptr, grid, pk->npair.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipDeviceSynchronize());
@@ -521,6 +521,8 @@ static void build_fb_tables_body(pai_pubkey* pk) {
     } else {
         // digit-form fixed-base table for the base-n digit engine
         const int pnl = pk->penc_nl;
+        const auto fb_table = launcher(padic_enc_ops(pnl), &PadicEncOps::fb_table, "no digit-engine table kernel for this limb count");
+        const auto fb_expand = launcher(padic_enc_ops(pnl), &PadicEncOps::fb_expand, "no digit-engine table kernel for this limb count");
         const Limbs Rm = hbn::mod(hbn::shl(Limbs{1u}, hbn::RB * pnl), pk->nsq);
         uint32_t* d_one = pk->d_one_dig;
         ScopedDevBuf d_hs, d_half;
@@ -553,7 +555,6 @@ static void build_fb_tables_body(pai_pubkey* pk) {
         pk->fbd_windows = DJ;
         HIP_CHECK(hipMalloc((void**)&pk->d_fb_dig, ((size_t)DJ << dwb) * ent_bytes));
         pk->fb_bytes += ((size_t)DJ << dwb) * ent_bytes;
-        bool ok = true;
         // window bases hs^(2^(h j)): one chain of squarings on the integer-per-wavefront geometry (k_sq_chain, ~6 us per
         // product) instead of the same chain walked by every lane of the table kernel at 50 us per product
         const int h1 = dwb <= 12 ? dwb : dwb / 2, J1 = dwb <= 12 ? DJ : 2 * DJ;
@@ -574,22 +575,20 @@ static void build_fb_tables_body(pai_pubkey* pk) {
             fbb.nd = pk->ct_nd;
         }
         if (dwb <= 12) {
-            ok = launch_fb_table_padic(pnl, nullptr, pk->nmod.d_ctx, pk->d_nm1, d_hs.as<uint32_t>(), d_one, pk->d_fb_dig, DJ, dwb, fbb);
+            fb_table(nullptr, pk->nmod.d_ctx, pk->d_nm1, d_hs.as<uint32_t>(), d_one, pk->d_fb_dig, DJ, dwb, fbb);
         } else {
             // two levels: half-width windows at twice the density (sequential chains of 2^h entries), then
             // one parallel pass of DJ * 2^dwb independent products
             const int h = dwb / 2;
             d_half.ensure(((size_t)(2 * DJ) << h) * ent_bytes);
-            ok = launch_fb_table_padic(pnl, nullptr, pk->nmod.d_ctx, pk->d_nm1, d_hs.as<uint32_t>(), d_one, d_half.as<uint32_t>(), 2 * DJ, h, fbb) &&
-                 launch_fb_expand_padic(pnl, nullptr, pk->dev.ncu, pk->nmod.d_ctx, pk->d_nm1, d_half.as<uint32_t>(), pk->d_fb_dig, DJ, h,
-                                        pk->d_mscratch);
+            fb_table(nullptr, pk->nmod.d_ctx, pk->d_nm1, d_hs.as<uint32_t>(), d_one, d_half.as<uint32_t>(), 2 * DJ, h, fbb);
+            fb_expand(nullptr, pk->dev.ncu, pk->nmod.d_ctx, pk->d_nm1, d_half.as<uint32_t>(), pk->d_fb_dig, DJ, h, pk->d_mscratch);
         }
         hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
         d_hs.release();
         d_half.release();
         d_bases.release();
         d_hs_plain.release();
-        if (!ok) throw PaiError(PAI_E_INTERNAL, "no digit-engine table kernel for this limb count");
         HIP_CHECK(e1);
         HIP_CHECK(e2);
         pk->fb_gform = false;

@@ -25,8 +25,8 @@ static void ctmul_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint32
     Q.e_bcast = e_bcast;
     OrderScope order_5(pk->order, s);
     ScopedKernelTimer t(timer_name, s, "padic");
-    if (!launch_ctmul_padic(pk->penc_nl, s, grid, Q, d_ct, d_e, d_out, (int)N))
-        throw PaiError(PAI_E_INTERNAL, "no digit-engine ct*pt kernel for this limb count");
+    launcher(padic_enc_ops(pk->penc_nl), &PadicEncOps::ctmul, "no digit-engine ct*pt kernel for this limb count")(
+        s, grid, Q, d_ct, d_e, d_out, (int)N);
     t.stop();
     HIP_CHECK(hipGetLastError());
     order_5.done();
@@ -68,8 +68,8 @@ static void ctmul_pair_locked(const pai_pubkey* pk, hipStream_t s, int nl, const
     P.r_words = pk->r_words;
     OrderScope order_(pk->order, s);
     ScopedKernelTimer t("k_ctmul", s, path);
-    if (!launch_pair_ctmul(nl, s, pgrid, Q, d_ct, d_e, pk->pair_wv.as<uint32_t>(), (int)N))
-        throw PaiError(PAI_E_INTERNAL, "no digit-pair ct * pt kernel for this limb count");
+    launcher(pair_ops(nl), &PairOps::ctmul, "no digit-pair ct * pt kernel for this limb count")(
+        s, pgrid, Q, d_ct, d_e, pk->pair_wv.as<uint32_t>(), (int)N);
     g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), out_words, nullptr, d_out, (int)N, 0);
     t.stop();
     HIP_CHECK(hipGetLastError());

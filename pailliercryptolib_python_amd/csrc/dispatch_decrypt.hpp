@@ -295,8 +295,8 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
             Q.out_words = M.out_words;
             {
                 ScopedKernelTimer t("k_dec_a", s, "pair4");
-                if (!launch_pair_ctmul(M.nl, s, pgrid, Q, d_ct, sk->d_expo[0], M.wv[0].as<uint32_t>(), (int)N))
-                    throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this prime size");
+                launcher(pair_ops(M.nl), &PairOps::ctmul, "no digit-pair kernel for this prime size")(
+                    s, pgrid, Q, d_ct, sk->d_expo[0], M.wv[0].as<uint32_t>(), (int)N);
                 for (int w = 0; w < 2; ++w) {
                     EncParams P{};
                     P.nsq = M.s2[w].d_ctx;

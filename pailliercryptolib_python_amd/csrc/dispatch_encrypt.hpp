@@ -37,8 +37,8 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu * 8));
             OrderScope order_2(pk->order, s);
             ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s, "pair4");
-            if (!launch_pair_fixed_base(pk->midp_nl, s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0))
-                throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this limb count");
+            launcher(pair_ops(pk->midp_nl), &PairOps::fixed_base, "no digit-pair kernel for this limb count")(
+                s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0);
             g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), pk->midp_out_words, d_ct_in, d_ct_out, (int)N, from_plain ? 0 : 1);
             t.stop();
             HIP_CHECK(hipGetLastError());
@@ -175,8 +175,8 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
         ScopedKernelTimer t(!from_plain ? "k_encrypt(obfuscate)" : (d_r ? "k_encrypt(djn)" : "k_encrypt(raw)"), s, "padic");
-        if (!launch_encrypt_padic(pk->penc_nl, s, pgrid, Q, d_m, d_r, d_ct_in, d_ct_out, (int)N, !from_plain ? 2 : (d_r ? 1 : 0)))
-            throw PaiError(PAI_E_INTERNAL, "no digit-engine encrypt kernel for this limb count");
+        launcher(padic_enc_ops(pk->penc_nl), &PadicEncOps::encrypt, "no digit-engine encrypt kernel for this limb count")(
+            s, pgrid, Q, d_m, d_r, d_ct_in, d_ct_out, (int)N, !from_plain ? 2 : (d_r ? 1 : 0));
         t.stop();
     } else if (pk->pair_nl && d_r && pk->djn) {
         // DJN encryption / obfuscation on lane-group digit pairs: (w, v) = plain pair of hs^r (1 + m n) [or hs^r], then
@@ -196,8 +196,8 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         const size_t tiles = (N + epb - 1) / epb;
         const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu * 2));
         ScopedKernelTimer t(from_plain ? "k_encrypt(djn)" : "k_encrypt(obfuscate)", s, "pair");
-        if (!launch_pair_fixed_base(pk->pair_nl, s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0))
-            throw PaiError(PAI_E_INTERNAL, "no digit-pair kernel for this limb count");
+        launcher(pair_ops(pk->pair_nl), &PairOps::fixed_base, "no digit-pair kernel for this limb count")(
+            s, pgrid, Q, d_m, d_r, pk->pair_wv.as<uint32_t>(), (int)N, from_plain ? 1 : 0);
         g->pair_finish(s, grid, P, pk->pair_wv.as<uint32_t>(), pk->pair_out_words, d_ct_in, d_ct_out, (int)N, from_plain ? 0 : 1);
         t.stop();
     } else if (d_r == nullptr) {
@@ -229,8 +229,8 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             Q.in_words = pk->n_words;
             Q.ct_words = pk->ct_words;
             ScopedKernelTimer t("k_pow(r^n)", s, "padic");
-            if (!launch_pow_padic(pk->penc_nl, s, pgrid, Q, d_r, pk->tmp.as<uint32_t>(), (int)N))
-                throw PaiError(PAI_E_INTERNAL, "no digit-engine power kernel for this limb count");
+            launcher(padic_enc_ops(pk->penc_nl), &PadicEncOps::pow, "no digit-engine power kernel for this limb count")(
+                s, pgrid, Q, d_r, pk->tmp.as<uint32_t>(), (int)N);
             t.stop();
         } else {
             pk->table.ensure(g->table_words((size_t)grid) * 4);

@@ -83,8 +83,7 @@ static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint
         const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
         ScopedKernelTimer t("k_mexp_table", s);
-        if (!launch_mexp_table_padic(pnl, s, grid, Q, d_ct, nullptr, (int)N))
-            throw PaiError(PAI_E_INTERNAL, "no digit-form kernel for this limb count");
+        launcher(padic_enc_ops(pnl), &PadicEncOps::mexp_table, "no digit-form kernel for this limb count")(s, grid, Q, d_ct, nullptr, (int)N);
         t.stop();
         HIP_CHECK(hipGetLastError());
     }
@@ -92,8 +91,7 @@ static bool ct_pack_padic_locked(const pai_pubkey* pk, hipStream_t s, const uint
         const size_t tiles = (G + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
         ScopedKernelTimer t("k_ct_pack_padic", s);
-        if (!launch_ct_pack_padic(pnl, s, grid, Q, (int)N, count, step, d_out, (int)G))
-            throw PaiError(PAI_E_INTERNAL, "no pack kernel for this limb count");
+        launcher(padic_enc_ops(pnl), &PadicEncOps::ct_pack, "no pack kernel for this limb count")(s, grid, Q, (int)N, count, step, d_out, (int)G);
         t.stop();
         HIP_CHECK(hipGetLastError());
     }

@@ -256,8 +256,8 @@ int pai_ct_sparse_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uin
                         const size_t tl = N * nsigns, tiles = (tl + BLOCK_THREADS - 1) / BLOCK_THREADS;
                         const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
                         ScopedKernelTimer t("k_mexp_table", s);
-                        if (!launch_mexp_table_padic(pnl, s, grid, Q, d_ct, d_ct_inv, (int)tl))
-                            throw PaiError(PAI_E_INTERNAL, "no multi-exponentiation kernel for this limb count");
+                        launcher(padic_enc_ops(pnl), &PadicEncOps::mexp_table, "no multi-exponentiation kernel for this limb count")(
+                            s, grid, Q, d_ct, d_ct_inv, (int)tl);
                         t.stop();
                         HIP_CHECK(hipGetLastError());
                     }
@@ -265,8 +265,8 @@ int pai_ct_sparse_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uin
                         const size_t tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
                         const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
                         ScopedKernelTimer t("k_smexp", s);
-                        if (!launch_smexp_padic(pnl, s, grid, Q, A, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes))
-                            throw PaiError(PAI_E_INTERNAL, "no multi-exponentiation kernel for this limb count");
+                        launcher(padic_enc_ops(pnl), &PadicEncOps::smexp, "no multi-exponentiation kernel for this limb count")(
+                            s, grid, Q, A, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes);
                         t.stop();
                         HIP_CHECK(hipGetLastError());
                     }
@@ -367,8 +367,8 @@ int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
                 const size_t tl = bases * nsigns, tiles = (tl + BLOCK_THREADS - 1) / BLOCK_THREADS;
                 const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
                 ScopedKernelTimer t("k_mexp_table", s);
-                if (!launch_mexp_table_padic(pnl, s, grid, Q, d_ct, d_ct_inv, (int)tl))
-                    throw PaiError(PAI_E_INTERNAL, "no multi-exponentiation kernel for this limb count");
+                launcher(padic_enc_ops(pnl), &PadicEncOps::mexp_table, "no multi-exponentiation kernel for this limb count")(
+                    s, grid, Q, d_ct, d_ct_inv, (int)tl);
                 t.stop();
                 HIP_CHECK(hipGetLastError());
             }
@@ -376,8 +376,8 @@ int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
                 const size_t tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
                 const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
                 ScopedKernelTimer t("k_mexp", s);
-                if (!launch_mexp_padic(pnl, s, grid, Q, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes))
-                    throw PaiError(PAI_E_INTERNAL, "no multi-exponentiation kernel for this limb count");
+                launcher(padic_enc_ops(pnl), &PadicEncOps::mexp, "no multi-exponentiation kernel for this limb count")(
+                    s, grid, Q, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes);
                 t.stop();
                 HIP_CHECK(hipGetLastError());
             }

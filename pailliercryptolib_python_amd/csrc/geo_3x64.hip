@@ -12,13 +12,7 @@ template <class GC>
 static void launch_pp(hipStream_t s, int n, int gy, bool var, const DecPPParams& P, const uint32_t* ct, uint32_t* out) {
     using GP = Geo<3, 64, 3, false, true>;
     constexpr int bytes = PPLds<GP, GC>::BYTES;
-    if (var) {
-        (void)hipFuncSetAttribute((const void*)k_ctmul_pp<GP, GC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        hipLaunchKernelGGL((k_ctmul_pp<GP, GC>), dim3(n, gy), dim3(BLOCK_THREADS), bytes, s, P, ct, out, n);
-    } else {
-        (void)hipFuncSetAttribute((const void*)k_dec_a_pp<GP, GC>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        hipLaunchKernelGGL((k_dec_a_pp<GP, GC>), dim3(n, gy), dim3(BLOCK_THREADS), bytes, s, P, ct, out, n);
-    }
+    launch(var ? k_ctmul_pp<GP, GC> : k_dec_a_pp<GP, GC>, dim3(n, gy), dim3(BLOCK_THREADS), bytes, s, P, ct, out, n);
 }
 void launch_dec_a_pp(hipStream_t s, int n, const DecPPParams& P, const uint32_t* ct, uint32_t* u_out, int chain_limbs) {
     if (chain_limbs == 1) launch_pp<Geo<1, 64, 1, false, true>>(s, n, 2, false, P, ct, u_out);

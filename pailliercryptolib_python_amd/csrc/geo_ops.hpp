@@ -114,31 +114,34 @@ struct FbBases {
     const uint32_t* kdig = nullptr;      // digit pairs of R^(i+2) mod n^2 (the ciphertext -> digit-form constants)
     int nd = 0;
 };
-bool launch_fb_table_padic(int nl, hipStream_t s, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* hs_dig,
-                           const uint32_t* one_dig, uint32_t* table, int J, int wb, const FbBases& fb);
-bool launch_fb_expand_padic(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S,
-                            uint32_t* T, int J, int h, uint32_t* mscratch);
 struct PowPadicParams;
-bool launch_pow_padic(int nl, hipStream_t s, int grid, const PowPadicParams& P, const uint32_t* base, uint32_t* out, int n);
 struct CtMulPadicParams;
-size_t ctmul_padic_table_words(int nl, int wbits, size_t blocks);
-bool launch_ctmul_padic(int nl, hipStream_t s, int grid, const CtMulPadicParams& P, const uint32_t* ct, const uint32_t* e,
-                        uint32_t* out, int n);
 struct MexpPadicParams;
-bool launch_mexp_table_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* ct, const uint32_t* ct_inv, int nlanes);
-bool launch_mexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
-bool launch_smexp_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, const SmexpArgs& S, const uint32_t* e,
-                        const uint8_t* sign, uint32_t* out, int nlanes);
-bool launch_ct_pack_padic(int nl, hipStream_t s, int grid, const MexpPadicParams& P, int nrows, int slots, int slot_bits, uint32_t* out,
-                          int nlanes);
-// g-factoring of a finished digit-form table (kernels_padic_enc.hpp): passes 1 and 2 over `count` entries in chunks of K
+size_t ctmul_padic_table_words(int nl, int wbits, size_t blocks);
 bool padic_enc_gform_supported();
-bool launch_fb_g_prefix_padic(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K,
-                              uint32_t* pref, uint32_t* tot, int tw, uint32_t* mscratch);
-bool launch_fb_g_finish_padic(int nl, hipStream_t s, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K,
-                              const uint32_t* pref, const uint32_t* inv, int tw, uint32_t* mscratch);
-bool launch_encrypt_padic(int nl, hipStream_t s, int grid, const EncPadicParams& P, const uint32_t* m, const uint32_t* r,
-                          const uint32_t* ct_in, uint32_t* ct_out, int n, int mode);
+// the digit engine's launchers for one limb count (padic_enc_launch.hpp fills one table per translation unit)
+struct PadicEncOps {
+    void (*fb_table)(hipStream_t, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* hs_dig, const uint32_t* one_dig,
+                     uint32_t* table, int J, int wb, const FbBases& fb);
+    void (*fb_expand)(hipStream_t, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S, uint32_t* T, int J, int h,
+                      uint32_t* mscratch);
+    void (*encrypt)(hipStream_t, int grid, const EncPadicParams&, const uint32_t* m, const uint32_t* r, const uint32_t* ct_in,
+                    uint32_t* ct_out, int n, int mode);
+    // g-factoring of a finished digit-form table (kernels_padic_enc.hpp): passes 1 and 2 over `count` entries in chunks of K
+    void (*g_prefix)(hipStream_t, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K, uint32_t* pref,
+                     uint32_t* tot, int tw, uint32_t* mscratch);
+    void (*g_finish)(hipStream_t, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K, const uint32_t* pref,
+                     const uint32_t* inv, int tw, uint32_t* mscratch);
+    void (*ctmul)(hipStream_t, int grid, const CtMulPadicParams&, const uint32_t* ct, const uint32_t* e, uint32_t* out, int n);
+    void (*pow)(hipStream_t, int grid, const PowPadicParams&, const uint32_t* base, uint32_t* out, int n);
+    void (*mexp_table)(hipStream_t, int grid, const MexpPadicParams&, const uint32_t* ct, const uint32_t* ct_inv, int nlanes);
+    void (*mexp)(hipStream_t, int grid, const MexpPadicParams&, const uint32_t* e, const uint8_t* sign, uint32_t* out, int nlanes);
+    void (*smexp)(hipStream_t, int grid, const MexpPadicParams&, const SmexpArgs&, const uint32_t* e, const uint8_t* sign,
+                  uint32_t* out, int nlanes);
+    void (*ct_pack)(hipStream_t, int grid, const MexpPadicParams&, int nrows, int slots, int slot_bits, uint32_t* out, int nlanes);
+};
+const PadicEncOps* padic_enc_ops(int nl);         // 36 / 72 limbs, nullptr = not served
+const PadicEncOps* padic_enc_ops_36();            // (padic_enc36_kernels.hip)
 
 // digit pairs with base n on the lane-group engine (kernels_pair.hpp): DJN obfuscator / encryption for n of 2049 .. 4156 bits
 struct PairParams;
@@ -146,18 +149,21 @@ struct PairCtMulParams;
 int pair_nl_for_n_bits(int bits);                 // 112 / 144 limbs, 0 = not served
 int pair_nl_for_prime_bits(int bits);             // 36 / 56 / 72 limbs (primes of keys up to 2048 / 3072 / 4096 bits), 0 = not served
 int pair_epb(int nl);                             // elements per workgroup
-bool launch_pair_fb_chain(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* bases,
-                          const uint32_t* one_pair, uint32_t* S, int nwin, int h, const FbBases& fb);
-bool launch_pair_fb_expand(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S,
-                           uint32_t* T, int J, int h);
-bool launch_pair_g_prefix(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K,
-                          uint32_t* pref, uint32_t* tot, int tw);
-bool launch_pair_g_finish(int nl, hipStream_t s, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K,
-                          const uint32_t* pref, const uint32_t* inv, int tw);
-bool launch_pair_fixed_base(int nl, hipStream_t s, int grid, const PairParams& P, const uint32_t* m, const uint32_t* r,
-                            uint32_t* wv_out, int n, int with_m);
-bool launch_pair_ctmul(int nl, hipStream_t s, int grid, const PairCtMulParams& P, const uint32_t* ct, const uint32_t* e,
-                       uint32_t* wv_out, int n);
+// the pair kernels' launchers for one limb count; a member the limb count does not instantiate is nullptr (the table
+// kernels exist at 112 / 144 limbs only)
+struct PairOps {
+    void (*fb_chain)(hipStream_t, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* bases,
+                     const uint32_t* one_pair, uint32_t* S, int nwin, int h, const FbBases& fb);
+    void (*fb_expand)(hipStream_t, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S, uint32_t* T, int J, int h);
+    void (*g_prefix)(hipStream_t, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K, uint32_t* pref,
+                     uint32_t* tot, int tw);
+    void (*g_finish)(hipStream_t, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K, const uint32_t* pref,
+                     const uint32_t* inv, int tw);
+    void (*fixed_base)(hipStream_t, int grid, const PairParams&, const uint32_t* m, const uint32_t* r, uint32_t* wv_out, int n,
+                       int with_m);
+    void (*ctmul)(hipStream_t, int grid, const PairCtMulParams&, const uint32_t* ct, const uint32_t* e, uint32_t* wv_out, int n);
+};
+const PairOps* pair_ops(int nl);                  // 36 / 56 / 72 / 112 / 144 limbs, nullptr = not served
 
 // x = a^-1 mod M for `count` values of `words` 32-bit words each (words in {64,128,192,256}); *fail counts
 // non-invertible inputs.  Returns false if `words` has no instantiation.

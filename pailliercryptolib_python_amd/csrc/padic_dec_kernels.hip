@@ -2,6 +2,7 @@
 // (seconds of compile time each) and their scheduler flags can be varied independently (build.py).
 #include "geo_ops.hpp"
 #include "kernels_padic.hpp"
+#include "launch.hpp"
 
 namespace pai {
 
@@ -22,9 +23,8 @@ size_t padic_scratch_words(int nl, size_t blocks) { return nl <= 36 ? 0 : (size_
 template <int NL, int U, int MODE>
 static void launch_padic(hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table) {
     constexpr int bytes = (MODE == PADIC_WBUF ? 2 : 3) * NL * BLOCK_THREADS * 4 + 2 * NL * 4;
-    (void)hipFuncSetAttribute((const void*)k_dec_a_padic<NL, U, MODEXP_WINDOW, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipLaunchKernelGGL((k_dec_a_padic<NL, U, MODEXP_WINDOW, MODE>), dim3(gridx, 2), dim3(BLOCK_THREADS), bytes, s, P, ct, u_out, n,
-                       reinterpret_cast<uint4*>(table));
+    launch(k_dec_a_padic<NL, U, MODEXP_WINDOW, MODE>, dim3(gridx, 2), dim3(BLOCK_THREADS), bytes, s, P, ct, u_out, n,
+           reinterpret_cast<uint4*>(table));
 }
 bool launch_dec_a_padic(int nl, hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct,
                         uint32_t* u_out, int n, uint32_t* table) {

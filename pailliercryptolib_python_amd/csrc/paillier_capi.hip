@@ -42,6 +42,14 @@ struct PaiError : std::runtime_error {
             throw PaiError(PAI_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));                \
     } while (0)
 
+// a launcher out of a per-limb-count table (padic_enc_ops / pair_ops, geo_ops.hpp): a limb count without a table or a table
+// without this kernel is an internal error, never a null call
+template <class Ops, class F>
+F launcher(const Ops* ops, F Ops::*member, const char* what) {
+    if (!ops || !(ops->*member)) throw PaiError(PAI_E_INTERNAL, what);
+    return ops->*member;
+}
+
 template <class F>
 int guarded(F&& f) {
     try {

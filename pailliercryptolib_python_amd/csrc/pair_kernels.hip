@@ -4,45 +4,36 @@
 // ~310 registers: 1.6 KB of scratch per lane with the table prefetch).
 #include "geo_ops.hpp"
 #include "kernels_pair.hpp"
+#include "launch.hpp"
 
 namespace pai {
 
 template <class G>
 struct PairLaunch {
-    static constexpr int BYTES = PairLds<G>::BYTES;
-    static void set_lds(const void* fn) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES); }
     static void chain(hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* bases,
                       const uint32_t* one_pair, uint32_t* S, int nwin, int h, const FbBases& fb) {
-        set_lds((const void*)k_pair_fb_chain<G>);
-        hipLaunchKernelGGL(k_pair_fb_chain<G>, dim3(grid), dim3(BLOCK_THREADS), BYTES, s, nctx, nm1, bases, one_pair, S, nwin, h,
-                           fb.bases_plain, fb.base_words, fb.kdig, fb.nd);
+        launch(k_pair_fb_chain<G>, dim3(grid), dim3(BLOCK_THREADS), PairLds<G>::BYTES, s, nctx, nm1, bases, one_pair, S, nwin, h,
+               fb.bases_plain, fb.base_words, fb.kdig, fb.nd);
     }
     static void expand(hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S, uint32_t* T, int J, int h) {
-        set_lds((const void*)k_pair_fb_expand<G>);
-        hipLaunchKernelGGL(k_pair_fb_expand<G>, dim3(grid), dim3(BLOCK_THREADS), BYTES, s, nctx, nm1, S, T, J, h);
+        launch(k_pair_fb_expand<G>, dim3(grid), dim3(BLOCK_THREADS), PairLds<G>::BYTES, s, nctx, nm1, S, T, J, h);
     }
     static void fixed_base(hipStream_t s, int grid, const PairParams& P, const uint32_t* m, const uint32_t* r, uint32_t* wv_out,
                            int n, int with_m) {
-        auto go = [&](auto kernel, int bytes) {
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK_THREADS), bytes, s, P, m, r, wv_out, n, with_m);
-        };
+        auto go = [&](auto kernel, int bytes) { launch(kernel, dim3(grid), dim3(BLOCK_THREADS), bytes, s, P, m, r, wv_out, n, with_m); };
         if (P.fb_gform) go(k_pair_fixed_base<G, true>, PairLds<G>::BYTES_FBG);
         else go(k_pair_fixed_base<G, false>, PairLds<G>::BYTES_FB);
     }
     static void g_prefix(hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K, uint32_t* pref,
                          uint32_t* tot, int tw) {
-        (void)hipFuncSetAttribute((const void*)k_pair_g_prefix<G>, hipFuncAttributeMaxDynamicSharedMemorySize, PairGLds<G>::BYTES);
-        hipLaunchKernelGGL(k_pair_g_prefix<G>, dim3(grid), dim3(BLOCK_THREADS), PairGLds<G>::BYTES, s, nctx, table, count, K, pref, tot, tw);
+        launch(k_pair_g_prefix<G>, dim3(grid), dim3(BLOCK_THREADS), PairGLds<G>::BYTES, s, nctx, table, count, K, pref, tot, tw);
     }
     static void g_finish(hipStream_t s, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K, const uint32_t* pref,
                          const uint32_t* inv, int tw) {
-        (void)hipFuncSetAttribute((const void*)k_pair_g_finish<G>, hipFuncAttributeMaxDynamicSharedMemorySize, PairGLds<G>::BYTES);
-        hipLaunchKernelGGL(k_pair_g_finish<G>, dim3(grid), dim3(BLOCK_THREADS), PairGLds<G>::BYTES, s, nctx, table, count, K, pref, inv, tw);
+        launch(k_pair_g_finish<G>, dim3(grid), dim3(BLOCK_THREADS), PairGLds<G>::BYTES, s, nctx, table, count, K, pref, inv, tw);
     }
     static void ctmul(hipStream_t s, int grid, const PairCtMulParams& P, const uint32_t* ct, const uint32_t* e, uint32_t* wv_out, int n) {
-        (void)hipFuncSetAttribute((const void*)k_pair_ctmul<G>, hipFuncAttributeMaxDynamicSharedMemorySize, PairLds<G>::BYTES_CT);
-        hipLaunchKernelGGL(k_pair_ctmul<G>, dim3(grid, P.nctx1 ? 2 : 1), dim3(BLOCK_THREADS), PairLds<G>::BYTES_CT, s, P, ct, e, wv_out, n);
+        launch(k_pair_ctmul<G>, dim3(grid, P.nctx1 ? 2 : 1), dim3(BLOCK_THREADS), PairLds<G>::BYTES_CT, s, P, ct, e, wv_out, n);
     }
 };
 #ifndef PAIR_G112
@@ -78,55 +69,37 @@ int pair_nl_for_n_bits(int bits) {
 }
 int pair_nl_for_prime_bits(int bits) { return RB * 36 >= bits + 20 ? 36 : (RB * 56 >= bits + 20 ? 56 : (RB * 72 >= bits + 20 ? 72 : 0)); }
 int pair_epb(int nl) { return nl == 112 ? G112::EPB : (nl == 144 ? G144::EPB : (nl == 36 || nl == 56 || nl == 72 ? G36::EPB : 0)); }
-bool launch_pair_fb_chain(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* bases,
-                          const uint32_t* one_pair, uint32_t* S, int nwin, int h, const FbBases& fb) {
-    if (nl == 112) P112::chain(s, grid, nctx, nm1, bases, one_pair, S, nwin, h, fb);
-    else if (nl == 144) P144::chain(s, grid, nctx, nm1, bases, one_pair, S, nwin, h, fb);
-    else return false;
-    return true;
+// the table kernels come with the n-sized geometries only: PC = the instantiation behind the g-factoring passes
+template <class P, class PC>
+static PairOps pair_ops_n() {
+    PairOps t{};
+    t.fb_chain = &P::chain;
+    t.fb_expand = &P::expand;
+    t.g_prefix = &PC::g_prefix;
+    t.g_finish = &PC::g_finish;
+    t.fixed_base = &P::fixed_base;
+    t.ctmul = &P::ctmul;
+    return t;
 }
-bool launch_pair_fb_expand(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* nm1, const uint32_t* S,
-                           uint32_t* T, int J, int h) {
-    if (nl == 112) P112::expand(s, grid, nctx, nm1, S, T, J, h);
-    else if (nl == 144) P144::expand(s, grid, nctx, nm1, S, T, J, h);
-    else return false;
-    return true;
+// (mid-size batches at keys up to 2048 bits: the one-element-per-lane engine's table has the same layout)
+template <class P>
+static PairOps pair_ops_prime() {
+    PairOps t{};
+    t.fixed_base = &P::fixed_base;
+    t.ctmul = &P::ctmul;
+    return t;
 }
-bool launch_pair_fixed_base(int nl, hipStream_t s, int grid, const PairParams& P, const uint32_t* m, const uint32_t* r,
-                            uint32_t* wv_out, int n, int with_m) {
-    if (nl == 112) P112::fixed_base(s, grid, P, m, r, wv_out, n, with_m);
-    else if (nl == 144) P144::fixed_base(s, grid, P, m, r, wv_out, n, with_m);
-    else if (nl == 36) P36::fixed_base(s, grid, P, m, r, wv_out, n, with_m);         // (mid-size batches at keys up to 2048 bits: the
-    else if (nl == 56) P56::fixed_base(s, grid, P, m, r, wv_out, n, with_m);         //  one-element-per-lane engine's table has the
-    else if (nl == 72) P72::fixed_base(s, grid, P, m, r, wv_out, n, with_m);         //  same layout)
-    else return false;
-    return true;
-}
-
-bool launch_pair_g_prefix(int nl, hipStream_t s, int grid, const MontCtx* nctx, const uint32_t* table, size_t count, int K,
-                          uint32_t* pref, uint32_t* tot, int tw) {
-    if (nl == 112) P112C::g_prefix(s, grid, nctx, table, count, K, pref, tot, tw);
-    else if (nl == 144) P144C::g_prefix(s, grid, nctx, table, count, K, pref, tot, tw);
-    else return false;
-    return true;
-}
-bool launch_pair_g_finish(int nl, hipStream_t s, int grid, const MontCtx* nctx, uint32_t* table, size_t count, int K,
-                          const uint32_t* pref, const uint32_t* inv, int tw) {
-    if (nl == 112) P112C::g_finish(s, grid, nctx, table, count, K, pref, inv, tw);
-    else if (nl == 144) P144C::g_finish(s, grid, nctx, table, count, K, pref, inv, tw);
-    else return false;
-    return true;
-}
-
-bool launch_pair_ctmul(int nl, hipStream_t s, int grid, const PairCtMulParams& P, const uint32_t* ct, const uint32_t* e,
-                       uint32_t* wv_out, int n) {
-    if (nl == 112) P112::ctmul(s, grid, P, ct, e, wv_out, n);
-    else if (nl == 144) P144::ctmul(s, grid, P, ct, e, wv_out, n);
-    else if (nl == 36) P36::ctmul(s, grid, P, ct, e, wv_out, n);
-    else if (nl == 56) P56::ctmul(s, grid, P, ct, e, wv_out, n);
-    else if (nl == 72) P72::ctmul(s, grid, P, ct, e, wv_out, n);
-    else return false;
-    return true;
+const PairOps* pair_ops(int nl) {
+    static const PairOps o112 = pair_ops_n<P112, P112C>(), o144 = pair_ops_n<P144, P144C>();
+    static const PairOps o36 = pair_ops_prime<P36>(), o56 = pair_ops_prime<P56>(), o72 = pair_ops_prime<P72>();
+    switch (nl) {
+        case 112: return &o112;
+        case 144: return &o144;
+        case 36: return &o36;
+        case 56: return &o56;
+        case 72: return &o72;
+        default: return nullptr;
+    }
 }
 
 }  // namespace pai

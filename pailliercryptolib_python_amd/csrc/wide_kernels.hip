@@ -2,15 +2,15 @@
 // 1158 bits (40 limbs) and up to 2086 bits (72 limbs).
 #include "geo_ops.hpp"
 #include "kernels_wide.hpp"
+#include "launch.hpp"
 
 namespace pai {
 
 template <int NL>
 static void launch_a(hipStream_t s, int gridx, const DecAParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table) {
     constexpr int bytes = NL * BLOCK_THREADS * 4;
-    (void)hipFuncSetAttribute((const void*)k_dec_a_wide<NL, MODEXP_WINDOW>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipLaunchKernelGGL((k_dec_a_wide<NL, MODEXP_WINDOW>), dim3(gridx, 2), dim3(BLOCK_THREADS), bytes, s, P, ct, u_out, n,
-                       reinterpret_cast<uint4*>(table));
+    launch(k_dec_a_wide<NL, MODEXP_WINDOW>, dim3(gridx, 2), dim3(BLOCK_THREADS), bytes, s, P, ct, u_out, n,
+           reinterpret_cast<uint4*>(table));
 }
 
 int wide_nl_for_bits(int bits) {
