@@ -166,6 +166,17 @@ int pai_obfuscate(const pai_pubkey* pk, uint32_t* d_ct, const uint32_t* d_r, siz
 /* ipclPrivateKey.decrypt(CipherText) — classes.cpp:127-133 (CRT).  d_m: [N][n_words]. */
 int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, void* stream);
 
+/* Owner-side encryption: pai_encrypt / pai_obfuscate by the party that holds p and q — the same bits for the same r.  Served
+ * calls (DJN keys whose primes the encryption digit engine accepts, batches from the hand-over edge `PAI_TUNE crtenc_min` on,
+ * PAI_DISABLE=crtenc not set) compute hs^r as two half-width fixed-base exponentiations modulo p^2 and q^2 and one Garner lift
+ * (k_crt_lift), then multiply 1 + m n [the ciphertext] in modulo n^2; every other call is the public call.  The base-p / base-q
+ * tables are built by the first served call and belong to the public handle's table set: same byte budget (PAI_FB_CACHE_MB), evicted
+ * with the public tables, freed by pai_pubkey_trim, rebuilt bit-identical. */
+int pai_encrypt_crt(pai_privkey* sk, const uint32_t* d_m, const uint32_t* d_r, size_t N, uint32_t* d_ct, void* stream);
+int pai_obfuscate_crt(pai_privkey* sk, uint32_t* d_ct, const uint32_t* d_r, size_t N, void* stream);
+/* The base-p / base-q tables held right now: bytes of both, window width and windows of each (zeros before the first served call). */
+int pai_privkey_crt_table_info(const pai_privkey* sk, size_t* table_bytes, int* window_bits, int* windows);
+
 /* ipclCipherText.__add__(ct, ct) — classes.cpp:318-321: d_out[i] = d_a[i] * d_b[i] mod n^2.
  * b_bcast != 0: d_b holds one ciphertext used for every i (size-1 broadcast).  d_out may alias d_a.
  * Operands are residues modulo n^2 (as everywhere in this ABI); the result is the canonical residue.  (Batches beyond the

@@ -64,6 +64,9 @@ PROTOTYPES = {
     "pai_encrypt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_obfuscate": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
     "pai_decrypt": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
+    "pai_encrypt_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
+    "pai_obfuscate_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
+    "pai_privkey_crt_table_info": (C.c_int, [voidp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pai_ct_add": (C.c_int, [voidp, voidp, voidp, C.c_int, C.c_size_t, voidp, voidp]),
     "pai_ct_mul": (C.c_int, [voidp, voidp, voidp, C.c_int, C.c_int, C.c_int, C.c_size_t, voidp, voidp]),
     "pai_ct_invert": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),

@@ -491,6 +491,24 @@ class ipclPrivateKey:
 
         return engine.gather_shards(engine.fan_out(devs, work, words.shape[0]), hpub.device)
 
+    # -- owner-side encryption (extension): the holder of p and q computes hs^r modulo p^2 and q^2 and lifts ------------------
+    def _single_device(self, count: int) -> bool:
+        return len(self._pk._device_list()) == 1 and self._pk.fanout_devices(count) is None
+
+    def encrypt_words(self, m: torch.Tensor, r: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ipclPublicKey.encrypt_words(m, True, r) — the same bits for the same r — through pai_encrypt_crt.  Keys on a
+        device list take the public route."""
+        if not self._single_device(m.shape[0]):
+            return self._pk.encrypt_words(m, True, r)
+        return self.handle.encrypt(m, self._pk._draw_r(m.shape[0]) if r is None else r)
+
+    def obfuscate_words_(self, ct: torch.Tensor, r: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ct_i <- ct_i * obf(r_i) in place, as PublicKeyHandle.obfuscate_, through pai_obfuscate_crt."""
+        r = self._pk._draw_r(ct.shape[0]) if r is None else r
+        if not self._single_device(ct.shape[0]) or ct.device != self.handle.pub.device:
+            return self._pk.handle.obfuscate_(ct, r)
+        return self.handle.obfuscate_(ct, r)
+
     @property
     def n(self):
         return ipclBigNumber(self._pk._n)

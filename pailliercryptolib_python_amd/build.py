@@ -38,6 +38,7 @@ SOURCES = [
     "padic_enc_kernels.hip",
     "padic_enc36_kernels.hip",
     "pair_kernels.hip",
+    "crt_lift_kernels.hip",
     "paillier_capi.hip",
 ]
 

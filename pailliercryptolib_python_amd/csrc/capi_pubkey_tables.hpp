@@ -275,10 +275,10 @@ static const ModSetup* lat_add_ctx(const pai_pubkey* pk, size_t N, bool tagged, 
 // extended GCD on the chunk totals): entries (a, d) become (a, t = d a^-1 mod n), after which every table product of an
 // encryption is the 4 NL^2 rule.  Slabs bound the scratch (one digit per entry).  PAI_DISABLE=gform keeps the plain table;
 // any failure (a non-unit would mean a broken key) leaves the table as it was built.
-static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
-    if (knob_disabled("gform")) return;
-    if (!padic_enc_gform_supported()) return;
-    const int pnl = pk->penc_nl;
+static bool gfactor_digit_rows(int pnl, const MontCtx* nctx, uint32_t* table, size_t NE, int dwb, int tw, const uint32_t* d_mod_words,
+                               uint32_t* d_mscratch, int ncu) {
+    if (knob_disabled("gform")) return false;
+    if (!padic_enc_gform_supported()) return false;
     const auto g_prefix = launcher(padic_enc_ops(pnl), &PadicEncOps::g_prefix, "no g-factoring kernel for this limb count");
     const auto g_finish = launcher(padic_enc_ops(pnl), &PadicEncOps::g_finish, "no g-factoring kernel for this limb count");
     // chunk length: divides the entries of a window, hence NE; one extended GCD per K entries.  64 measured best (first 2^20
@@ -287,8 +287,7 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
     if (long long v; knob_tune("fb_gform_k", &v)) {                     // a power of two up to the window's entry count
         if (v >= 2 && (v & (v - 1)) == 0 && (size_t)v <= ((size_t)1 << dwb)) K = (int)v;
     }
-    const int tw = pk->n_words;
-    if ((tw + 63) / 64 > 4) return;                                      // the totals are n_words wide: at most 4 words per lane of k_inv_eea_wave (inv_eea.hip serves up to 5)
+    if ((tw + 63) / 64 > 4) return false;                                // the totals are tw words wide: at most 4 words per lane of k_inv_eea_wave (inv_eea.hip serves up to 5)
     const size_t slab_max = (size_t)1 << 22;                             // entries per slab: 1.2 GB of prefix scratch at 72 limbs
     const size_t slab = std::min(NE, slab_max) / K * K;
     ScopedDevBuf d_pref, d_tot, d_inv, d_fail;
@@ -299,31 +298,35 @@ static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
         d_fail.ensure(4);
     } catch (const PaiError&) {
         (void)hipGetLastError();
-        return;
+        return false;
     }
     HIP_CHECK(hipMemset(d_fail.p, 0, 4));
-    const int grid = pk->dev.ncu;                                         // the scratch column is sized for this grid
+    const int grid = ncu;                                                 // the scratch column is sized for this grid
     const size_t ent_words = 2 * (size_t)pnl;
     // pass 1 and the inversions of every slab first (pass 2 overwrites the second digits: no partial conversion on failure)
     // -> with one slab of scratch the passes must alternate; a failure after some slabs were converted is handled by
     //    rebuilding (fb_ready stays false and the caller's catch frees the table)
     for (size_t e0 = 0; e0 < NE; e0 += slab) {
         const size_t cnt = std::min(slab, NE - e0);
-        uint32_t* tbl = pk->d_fb_dig + e0 * ent_words;
-        g_prefix(nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw, pk->d_mscratch);
+        uint32_t* tbl = table + e0 * ent_words;
+        g_prefix(nullptr, grid, nctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_tot.as<uint32_t>(), tw, d_mscratch);
         HIP_CHECK(hipGetLastError());
-        if (!launch_inv_eea(nullptr, tw, pk->d_nexp, d_tot.as<uint32_t>(), d_inv.as<uint32_t>(), (int)(cnt / K), 2 * 32 * tw + 64,
+        if (!launch_inv_eea(nullptr, tw, d_mod_words, d_tot.as<uint32_t>(), d_inv.as<uint32_t>(), (int)(cnt / K), 2 * 32 * tw + 64,
                             d_fail.as<int>()))
             throw PaiError(PAI_E_INTERNAL, "no extended-GCD instantiation for this key size");
         HIP_CHECK(hipGetLastError());
         int fail = 0;
         HIP_CHECK(hipMemcpy(&fail, d_fail.p, 4, hipMemcpyDeviceToHost));
         if (fail) throw PaiError(PAI_E_INTERNAL, "fixed-base table entry without an inverse modulo n");
-        g_finish(nullptr, grid, pk->nmod.d_ctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw, pk->d_mscratch);
+        g_finish(nullptr, grid, nctx, tbl, cnt, K, d_pref.as<uint32_t>(), d_inv.as<uint32_t>(), tw, d_mscratch);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipDeviceSynchronize());
-    pk->fb_gform = true;
+    return true;
+}
+static void gfactor_digit_table(pai_pubkey* pk, size_t NE, int dwb) {
+    if (gfactor_digit_rows(pk->penc_nl, pk->nmod.d_ctx, pk->d_fb_dig, NE, dwb, pk->n_words, pk->d_nexp, pk->d_mscratch, pk->dev.ncu))
+        pk->fb_gform = true;
 }
 
 // the same for the lane-group pair table of keys above 2048 bits (kernels_pair.hpp: k_pair_g_prefix / k_pair_g_finish)
@@ -385,10 +388,17 @@ static size_t fb_cache_budget(size_t mem_total) {
     if (const char* env = std::getenv("PAI_FB_CACHE_MB")) { double v = std::atof(env); if (v >= 1.0) return (size_t)(v * 1048576.0); }
     return mem_total / 2;
 }
+static void fb_free_crt_tables(pai_pubkey* pk) {      // the base-p / base-q tables of the owner-side CRT encryption go with the public ones
+    for (int w = 0; w < 2; ++w)
+        if (pk->d_crt_fb[w]) { (void)hipFree(pk->d_crt_fb[w]); pk->d_crt_fb[w] = nullptr; }
+    pk->crt_fb_ready = false;
+    pk->crt_fb_bytes = 0;
+}
 static void fb_free_tables(pai_pubkey* pk) {          // caller holds pk->mu and has synchronised the device
     if (pk->d_fb) { (void)hipFree(pk->d_fb); pk->d_fb = nullptr; }
     if (pk->d_fb_dig) { (void)hipFree(pk->d_fb_dig); pk->d_fb_dig = nullptr; }
     if (pk->d_pair_fb) { (void)hipFree(pk->d_pair_fb); pk->d_pair_fb = nullptr; }
+    fb_free_crt_tables(pk);
     pk->fb_ready = false;
     pk->fb_bytes = 0;
 }
@@ -441,7 +451,14 @@ static void fb_drop_tables(pai_pubkey* pk) {           // a failed build leaves 
     if (pk->d_pair_fb) { (void)hipFree(pk->d_pair_fb); pk->d_pair_fb = nullptr; }
     if (pk->d_fb) { (void)hipFree(pk->d_fb); pk->d_fb = nullptr; }
     pk->fb_ready = false;
-    pk->fb_bytes = 0;
+    pk->fb_bytes = pk->crt_fb_bytes;               // (the CRT-encryption tables of the key, if built, stay and stay registered)
+}
+// enters pk's table bytes in the per-device LRU (most recently used); caller holds pk->mu
+static void fb_register(pai_pubkey* pk) {
+    std::lock_guard<std::mutex> g(g_fb.mu);
+    pk->fb_registered = pk->fb_bytes;
+    g_fb.lru.erase(std::remove(g_fb.lru.begin(), g_fb.lru.end(), pk), g_fb.lru.end());
+    g_fb.lru.push_back(pk);
 }
 static void build_fb_tables_body(pai_pubkey* pk);
 void build_fb_tables(const pai_pubkey* cpk) {
@@ -470,11 +487,9 @@ void build_fb_tables(const pai_pubkey* cpk) {
     fb_make_room(pk, need, mem_total_b);
     for (int attempt = 0;; ++attempt) {
         try {
-            pk->fb_bytes = 0;                           // the builders add what they allocate for the tables
+            pk->fb_bytes = pk->crt_fb_bytes;            // the builders add what they allocate for the tables
             build_fb_tables_body(pk);
-            std::lock_guard<std::mutex> g(g_fb.mu);
-            pk->fb_registered = pk->fb_bytes;
-            g_fb.lru.push_back(pk);
+            fb_register(pk);
             return;
         } catch (const PaiError& e) {
             // a failed build (out of memory under pressure, a HIP error between the table allocation and fb_ready) must not

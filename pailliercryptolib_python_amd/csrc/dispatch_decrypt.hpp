@@ -145,6 +145,7 @@ void pai_privkey_destroy(pai_privkey* sk) {
     }
     if (sk->lat.d_pinvqR) (void)hipFree(sk->lat.d_pinvqR);
     sk->lat.table.release();
+    release_crt(sk);
     sk->table.release();
     sk->wscratch.release();
     sk->ubuf.release();

@@ -165,6 +165,14 @@ struct PairOps {
 };
 const PairOps* pair_ops(int nl);                  // 36 / 56 / 72 / 112 / 144 limbs, nullptr = not served
 
+// Garner lift of the owner-side CRT encryption (kernels_crt_lift.hpp) on the lane-group geometry of q^2
+struct CrtLiftParams;
+struct CrtLiftOps {
+    int nl, epb;                                  // limbs of the geometry, elements per workgroup
+    void (*lift)(hipStream_t, int grid, const CrtLiftParams&, const uint32_t* c_in, uint32_t* ct_out, int n);
+};
+const CrtLiftOps* crt_lift_ops(int nl);           // 72 / 112 / 144 limbs (crt_lift_kernels.hip), nullptr = not served
+
 // x = a^-1 mod M for `count` values of `words` 32-bit words each (words in {64,128,192,256}); *fail counts
 // non-invertible inputs.  Returns false if `words` has no instantiation.
 bool launch_inv_eea(hipStream_t s, int words, const uint32_t* mod, const uint32_t* a, uint32_t* out, int count,

@@ -22,6 +22,7 @@
 #include "kernels_codec.hpp"
 #include "kernels_pack.hpp"
 #include "kernels_declat.hpp"
+#include "kernels_crt_lift.hpp"
 
 using namespace pai;
 using hbn::Limbs;
@@ -548,6 +549,13 @@ struct pai_pubkey {
     mutable size_t fb_bytes = 0;       // device bytes of the built tables (the per-device table cache accounts with it)
     mutable size_t fb_registered = 0;  // fb_bytes as entered in the per-device LRU: written and read under g_fb.mu only (other handles sum it)
     mutable size_t fb_table_budget = 0;  // non-zero: this build takes the small operating point (build_fb_tables)
+    // owner-side CRT encryption (dispatch_encrypt_crt.hpp): the digit-form fixed-base tables of hs mod p^2 / q^2 with base p / q.
+    // They live with the public tables — counted in fb_bytes, evicted, trimmed and freed with them — and are built by the first
+    // pai_encrypt_crt / pai_obfuscate_crt of a private-key handle of this key.
+    mutable uint32_t* d_crt_fb[2] = {nullptr, nullptr};
+    mutable bool crt_fb_ready = false, crt_gform = false;
+    mutable int crt_wbits = 0, crt_windows = 0;
+    mutable size_t crt_fb_bytes = 0;     // the part of fb_bytes these two tables account for
     // latency path of ct * pt (small batches): n^2 on a wide-group geometry, built by the first small call
     mutable bool lat_ready = false, lat_usable = false;
     mutable ModSetup lat_msq;
@@ -611,6 +619,29 @@ struct pai_privkey {
     int nops[2] = {0, 0};
     int padic_nd = 0;
     DevBuf table, ubuf;
+    // Owner-side CRT encryption (dispatch_encrypt_crt.hpp): constants of the encryption digit engine with base s = p, q and of
+    // the Garner lift modulo q^2; built by the first call the route serves (ensure_crt)
+    struct Crt {
+        bool tried = false, ok = false;
+        int nl = 0;                       // limbs of the digit engine for both primes
+        int sw = 0;                       // packed words of a residue modulo s^2 (covers q^2)
+        int nd = 0;                       // base-R digits of such a residue (window bases entering digit form)
+        Limbs hs_s[2];                    // hs mod s^2
+        ModSetup sdig[2];                 // s at nl limbs
+        uint32_t* d_sm1[2] = {nullptr, nullptr};     // s - 1
+        uint32_t* d_s2[2] = {nullptr, nullptr};      // s^2, 2 nl limbs
+        uint32_t* d_one[2] = {nullptr, nullptr};     // digit pair of R mod s^2
+        uint32_t* d_hs[2] = {nullptr, nullptr};      // digit pair of hs R mod s^2
+        uint32_t* d_kdig[2] = {nullptr, nullptr};    // [nd][2][nl] digit pairs of R^(i+2) mod s^2
+        uint32_t* d_swords[2] = {nullptr, nullptr};  // s as packed words (extended-GCD modulus of the g-factoring)
+        int s_words = 0;
+        ModSetup q2;                      // q^2 on its lane-group geometry (the lift)
+        uint32_t* d_p2 = nullptr;         // p^2
+        uint32_t* d_pinv2R = nullptr;     // (p^-2 mod q^2) R mod q^2
+        uint32_t* d_mscratch = nullptr;   // quotient-digit columns of the digit engine at nl limbs
+        DevBuf zeros, cs, lifted;         // all-zero message rows, the residues [2][N][sw], hs^r mod n^2 [N][ct_words]
+        size_t zeros_rows = 0;
+    } crt;
     // Mid-size batches: stage A as the lane-group digit-pair exponentiation (k_pair_ctmul: modulus s, exponent s - 1, 4 lanes x 9
     // limbs per chain, both primes in one launch), then w + v s on the s^2 geometry (k_pair_finish); built by the first such call
     struct Mid {
@@ -1129,6 +1160,7 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     if (pk->d_nm1) (void)hipFree(pk->d_nm1);
     if (pk->d_nsq29) (void)hipFree(pk->d_nsq29);
     if (pk->d_fb_dig) (void)hipFree(pk->d_fb_dig);
+    for (int w = 0; w < 2; ++w) if (pk->d_crt_fb[w]) (void)hipFree(pk->d_crt_fb[w]);
     if (pk->d_mscratch) (void)hipFree(pk->d_mscratch);
     if (pk->d_one_dig) (void)hipFree(pk->d_one_dig);
     if (pk->d_ct_kdig) (void)hipFree(pk->d_ct_kdig);
@@ -1340,6 +1372,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_reduce.hpp"
 #include "dispatch_scan.hpp"
 #include "dispatch_pack.hpp"
+#include "dispatch_encrypt_crt.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

@@ -110,6 +110,21 @@ static size_t enc_mid_max(size_t ncu, int n_bits) {
     return n_bits > 900 && n_bits <= 2048 ? 160 * ncu : 0;
 }
 
+// ---- owner-side CRT encryption (dispatch_encrypt_crt.hpp) ---------------------------------------------------------------------
+// pai_encrypt_crt / pai_obfuscate_crt take the two half-width exponentiations and the Garner lift from this many elements on; below,
+// and wherever the entry says never, they are the public route.  PAI_TUNE crtenc_min overrides (absolute elements, 0 = every
+// batch); PAI_DISABLE=crtenc leaves the route out.  The entries are filled from tools/crt_encrypt_time.py
+// (profiles/r07/crt_encrypt_time.jsonl): the route is the default for a key size only where its median beat the public route's by
+// more than the spread of the five repeats.
+constexpr size_t CRTENC_NEVER = (size_t)-1;
+static size_t crtenc_min(size_t ncu, int key_bits) {
+    long long v;
+    if (knob_tune("crtenc_min", &v) && v >= 0) return (size_t)v;
+    (void)ncu;
+    (void)key_bits;
+    return CRTENC_NEVER;                 // not measured yet on any key size: off by default
+}
+
 // ---- ct x pt ------------------------------------------------------------------------------------------------------------------
 static size_t lat_mul_pp_max(size_t ncu) {          // PAI_TUNE lat_mul_pp: largest batch of the four-wave digit-pair ct * pt (0 disables)
     long long v;                                    // 2048-bit keys, 53-bit exponents: 0.22 ms up to 256, 0.31 / 0.43 at 512 / 1 024 against 0.37 / 0.49

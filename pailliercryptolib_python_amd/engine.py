@@ -693,6 +693,31 @@ class PrivateKeyHandle:
         _native.check(self.lib.pai_decrypt(self.h, _ptr(ct), ct.shape[0], _ptr(out), _stream(self.pub.device)))
         return out
 
+    # -- owner-side encryption (pai_encrypt_crt / pai_obfuscate_crt): the bits of PublicKeyHandle.encrypt / obfuscate_ ----------
+    def encrypt(self, m: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        pub = self.pub
+        pub._chk(m, pub.n_words, "m")
+        pub._chk(r, pub.r_words, "r")
+        if r.shape[0] != m.shape[0]:
+            raise ValueError("m and r must have the same number of rows")
+        out = pub.empty_ct(m.shape[0]) if out is None else out
+        _native.check(self.lib.pai_encrypt_crt(self.h, _ptr(m), _ptr(r), m.shape[0], _ptr(out), _stream(pub.device)))
+        return out
+
+    def obfuscate_(self, ct: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+        pub = self.pub
+        pub._chk(ct, pub.ct_words, "ct")
+        pub._chk(r, pub.r_words, "r")
+        _native.check(self.lib.pai_obfuscate_crt(self.h, _ptr(ct), _ptr(r), ct.shape[0], _stream(pub.device)))
+        return ct
+
+    def crt_table_info(self) -> dict:
+        """The base-p / base-q fixed-base tables of the owner-side encryption held right now: {"bytes" (both), "window_bits",
+        "windows"} (zeros before the first served call and after an eviction or trim)."""
+        b, w, j = C.c_size_t(0), C.c_int(0), C.c_int(0)
+        _native.check(self.lib.pai_privkey_crt_table_info(self.h, C.byref(b), C.byref(w), C.byref(j)))
+        return {"bytes": int(b.value), "window_bits": int(w.value), "windows": int(j.value)}
+
 
 # ------------------------------------------------------------------------------------------------
 # handle cache and single-process multi-GPU fan-out

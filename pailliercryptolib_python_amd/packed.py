@@ -317,7 +317,7 @@ def _key_layout(public_key, slot_bits, slots) -> Layout:
 
 
 def encrypt_packed(public_key, values, *, exponent: int, value_bits: int, slot_bits: int, slots: Optional[int] = None,
-                   apply_obfuscator: bool = True) -> "PaillierPackedNumber":
+                   apply_obfuscator: bool = True, r: Optional[torch.Tensor] = None, _encrypt_words=None) -> "PaillierPackedNumber":
     """PaillierPublicKey.encrypt_packed: encode and pack on the device, then encrypt G = ceil(N / k) rows."""
     lay = _key_layout(public_key, slot_bits, slots)
     v = check_value_bits(value_bits, lay.slot_bits)
@@ -328,7 +328,8 @@ def encrypt_packed(public_key, values, *, exponent: int, value_bits: int, slot_b
     if x.size == 0:
         ct = h.empty_ct(0)
     else:
-        ct = pub.encrypt_words(_pack_plain(h, x, E, v, lay, "encrypt_packed"), apply_obfuscator, None)
+        ct = (pub.encrypt_words if _encrypt_words is None else _encrypt_words)(_pack_plain(h, x, E, v, lay, "encrypt_packed"),
+                                                                               apply_obfuscator, r)
     return PaillierPackedNumber(public_key, ipclCipherText(pub, ct), slot_bits=lay.slot_bits, slots=lay.slots, exponent=E,
                                 value_bits=v, length=x.shape[0])
 
@@ -469,12 +470,13 @@ class PaillierPackedNumber:
         """G: the ciphertexts of this container."""
         return self.__ct.getSize()
 
-    def apply_obfuscator(self, *, r: Optional[torch.Tensor] = None) -> None:
-        """Re-randomise the G ciphertexts in place (pack() and the arithmetic below return canonical residues)."""
+    def apply_obfuscator(self, *, r: Optional[torch.Tensor] = None, _obfuscate=None) -> None:
+        """Re-randomise the G ciphertexts in place (pack() and the arithmetic below return canonical residues).
+        (_obfuscate, private: PaillierPrivateKey.apply_obfuscator's route.)"""
         pub = self.public_key.pubkey
         ct = self.__ct._t.clone()
         if ct.shape[0]:
-            pub.handle.obfuscate_(ct, pub._draw_r(ct.shape[0]) if r is None else r)
+            (pub.handle.obfuscate_ if _obfuscate is None else _obfuscate)(ct, pub._draw_r(ct.shape[0]) if r is None else r)
         self.__ct = ipclCipherText(pub, ct, taint=self.__ct._taint)
 
     # -- arithmetic (slot-wise) ---------------------------------------------------------------------

@@ -101,16 +101,16 @@ class PaillierPublicKey:
         return self.encrypt(plaintext, apply_obfuscator=False)
 
     def encrypt_packed(self, values, *, exponent: int, value_bits: int, slot_bits: int, slots: Optional[int] = None,
-                       apply_obfuscator: bool = True) -> "PaillierPackedNumber":
+                       apply_obfuscator: bool = True, r: Optional[torch.Tensor] = None, _encrypt_words=None) -> "PaillierPackedNumber":
         """Extension (packed.py): `values` (a 1-D float64 / int64 array or list) as ceil(N / slots) ciphertexts that hold `slots`
         fixed-point values each — slots-fold fewer encryptions, decryptions and bytes.  Mantissas are rint(x 2^exponent) (ties to
         even) for floats, x << exponent for integers (exponent >= 0); a mantissa with |m| >= 2^value_bits, NaN or infinity is a
         ValueError.  slots: default the largest count with slots * slot_bits <= bits(n) - 2.  Encoding and packing run on the
-        device (pai_fp_pack), then the usual encryption."""
+        device (pai_fp_pack), then the usual encryption.  r injects the obfuscator randomness (one row per ciphertext)."""
         from . import packed as _packed
 
         return _packed.encrypt_packed(self, values, exponent=exponent, value_bits=value_bits, slot_bits=slot_bits, slots=slots,
-                                      apply_obfuscator=apply_obfuscator)
+                                      apply_obfuscator=apply_obfuscator, r=r, _encrypt_words=_encrypt_words)
 
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
@@ -134,13 +134,14 @@ class PaillierPublicKey:
         return m, (expos if expos is not None else expo_d.cpu().numpy())
 
     def encrypt(self, values: Union[np.ndarray, list, int, float], apply_obfuscator: bool = True, *,
-                r: Optional[Union[torch.Tensor, np.ndarray]] = None, _align_to=None) -> "PaillierEncryptedNumber":
+                r: Optional[Union[torch.Tensor, np.ndarray]] = None, _align_to=None, _encrypt_words=None) -> "PaillierEncryptedNumber":
         """ipcl_python.py:108-147.  Scalars, lists and 1-D arrays of ints/floats; anything else is a
         ValueError exactly as there (2-D arrays fail the per-element type check).
         _align_to (private; raw encryptions only — the plaintext operand of ct + plaintext): target exponents, one per
         element or a single one.  An element whose own exponent is lower is encoded AT its target: for a raw encryption
         ct^(2^d) = E_raw(m 2^d mod n), so the bits and exponents are those the reference's alignment
-        (ipcl_python.py:570-741) produces, without the squarings."""
+        (ipcl_python.py:570-741) produces, without the squarings.
+        _encrypt_words (private; PaillierPrivateKey.encrypt): stands in for ipclPublicKey.encrypt_words on one device."""
         if np.isscalar(values):
             values = [values]
         if isinstance(values, np.ndarray):
@@ -153,6 +154,7 @@ class PaillierPublicKey:
             raise ValueError("PaillierPublicKey.encrypt: input value(s) should be integer or float")
         pub = self.pubkey
         h = pub.handle
+        encrypt_words = pub.encrypt_words if _encrypt_words is None else _encrypt_words
         if isinstance(r, np.ndarray):
             r = engine.to_device_words(r, h.device)
         tgt = None
@@ -207,7 +209,7 @@ class PaillierPublicKey:
             m, expo_d = h.fp_encode_f64(engine.small_operands([x], h.device)[0])
             if x.shape[0] <= HOST_EXPO_MAX:
                 # small batches: every launch first — the exponents (a host rule, no read-back) are computed while the device works
-                ct = pub.encrypt_words(m, apply_obfuscator, r)
+                ct = encrypt_words(m, apply_obfuscator, r)
                 return PaillierEncryptedNumber(self, ipclCipherText(self.pubkey, ct), exponents=_fp.float64_exponents(x), length=len(values))
             expos = expo_d.cpu().numpy()
         elif is_i64:
@@ -219,7 +221,7 @@ class PaillierPublicKey:
             if tgt is not None:
                 residues, expos = _fp.align_encoded(residues, expos, tgt, self.n, self.max_int)
             m = engine.to_device_words(residues, h.device)
-        ct = pub.encrypt_words(m, apply_obfuscator, r)
+        ct = encrypt_words(m, apply_obfuscator, r)
         return PaillierEncryptedNumber(self, ipclCipherText(self.pubkey, ct), exponents=expos, length=len(values))
 
 
@@ -241,6 +243,37 @@ class PaillierPrivateKey:
             self.__max_int = key.max_int
         else:
             raise KeyError("PaillierPrivateKey: key should be either Private key or Public key (with p and q)")
+
+    # -- owner-side encryption (extension): the bits of the public key's encryption, computed with p and q -------------------
+    def _public(self) -> PaillierPublicKey:
+        pub = self.__dict__.get("_pub")
+        if pub is None or pub.pubkey is not self.prikey._pk:
+            pub = self.__dict__["_pub"] = PaillierPublicKey(self.prikey._pk)
+        return pub
+
+    def _encrypt_words(self, m, apply_obfuscator, r):
+        if not apply_obfuscator:
+            return self.prikey._pk.encrypt_words(m, False, None)
+        return self.prikey.encrypt_words(m, r)
+
+    def encrypt(self, values, apply_obfuscator: bool = True, *, r=None) -> "PaillierEncryptedNumber":
+        """PaillierPublicKey.encrypt by the holder of p and q: same validation, codec, exponents and draw of r, the same bits
+        for the same r; the obfuscator hs^r is two half-width exponentiations modulo p^2 and q^2 and a Garner lift
+        (pai_encrypt_crt) where the key and the batch are served, the public route otherwise.  apply_obfuscator=False is the
+        public raw encryption."""
+        return self._public().encrypt(values, apply_obfuscator, r=r, _encrypt_words=self._encrypt_words)
+
+    def encrypt_packed(self, values, *, exponent: int, value_bits: int, slot_bits: int, slots: Optional[int] = None,
+                       apply_obfuscator: bool = True, r=None) -> "PaillierPackedNumber":
+        """PaillierPublicKey.encrypt_packed with the obfuscator computed as in encrypt."""
+        return self._public().encrypt_packed(values, exponent=exponent, value_bits=value_bits, slot_bits=slot_bits, slots=slots,
+                                             apply_obfuscator=apply_obfuscator, r=r, _encrypt_words=self._encrypt_words)
+
+    def apply_obfuscator(self, enc, *, r=None) -> None:
+        """Re-randomise a PaillierEncryptedNumber or PaillierPackedNumber of this key in place (pai_obfuscate_crt)."""
+        if enc.public_key.n != self.__n:
+            raise ValueError("PaillierPrivateKey.apply_obfuscator: public key mismatch")
+        enc.apply_obfuscator(r=r, _obfuscate=self.prikey.obfuscate_words_)
 
     def __getstate__(self):
         return (self.prikey, self.__n, self.__max_int)
@@ -760,11 +793,11 @@ class PaillierEncryptedNumber:
             raise IndexError("exponent: idx out of range")
         return int(self._expo[idx])
 
-    def apply_obfuscator(self, *, r: Optional[torch.Tensor] = None):
-        """ipcl_python.py:342-346: re-randomise in place."""
+    def apply_obfuscator(self, *, r: Optional[torch.Tensor] = None, _obfuscate=None):
+        """ipcl_python.py:342-346: re-randomise in place.  (_obfuscate, private: PaillierPrivateKey.apply_obfuscator's route.)"""
         h = self._h()
         ct = self._w.clone()
-        h.obfuscate_(ct, self.public_key.pubkey._draw_r(ct.shape[0]) if r is None else r)
+        (h.obfuscate_ if _obfuscate is None else _obfuscate)(ct, self.public_key.pubkey._draw_r(ct.shape[0]) if r is None else r)
         self.__ipclCipherText = ipclCipherText(self.public_key.pubkey, ct, taint=self.__ipclCipherText._taint)
 
     def __getitem__(self, key: Union[int, slice]) -> "PaillierEncryptedNumber":
