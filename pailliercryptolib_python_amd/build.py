@@ -35,6 +35,7 @@ SOURCES = [
     "inv_eea.hip",
     "wide_kernels.hip",
     "padic_dec_kernels.hip",
+    "padic_dec_kmr_kernels.hip",
     "padic_enc_kernels.hip",
     "padic_enc36_kernels.hip",
     "pair_kernels.hip",

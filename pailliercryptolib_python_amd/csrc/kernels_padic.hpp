@@ -21,6 +21,7 @@ struct DecPadicParams {
     int ct_words, u_words;
     int sqr_kara;                // 36-limb primes: squarings by sqr_kara (MODE PADIC_LDS_K) instead of the row-wise sqr
     int mul_kara;                // ... and the products too, digits kept in registers between operations (MODE PADIC_LDS_KM)
+    int red_kara;                // ... and the quotient products of the reductions (MODE PADIC_LDS_KMR); needs mul_kara
 };
 
 // (A, B) <- Montgomery digit form of the packed integer `row` (row_words 32-bit words, any value < s^2 R-ish):
@@ -103,7 +104,12 @@ constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 //                   registers from the table build to the end of the schedule: a squaring or a product takes its operand
 //                   from the registers the previous one left it in, the right operand of a product is loaded once from the
 //                   table.  LDS serves the row-wise entry (padic_to_digit_form) and exit, which keep the quotient buffer.
-constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3;
+// MODE PADIC_LDS_KMR: PADIC_LDS_KM with the quotient products m p of the Montgomery reductions by Karatsuba columns too
+//                   (mont_padic.hpp: kara_pass<FORM, true>) in both passes of a squaring and the first pass of a product, and the
+//                   product streams of those three passes as one chain per column (PADIC_KMR_RED; which passes: measured,
+//                   profiles/r14/README.md).  Same kernel body, same LDS, same table.
+constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4;
+constexpr bool padic_reg_mode(int mode) { return mode == PADIC_LDS_KM || mode == PADIC_LDS_KMR; }
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict__ u_out, int n,
@@ -137,7 +143,7 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
     const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * BLOCK_THREADS + threadIdx.x;
     // M: quotient digits of the first half of the product rule: an LDS digit buffer, or (PADIC_WBUF) a strided global column
     const typename E::MBuf M = MODE == PADIC_WBUF ? typename E::MBuf{P.wscratch + slot, nslots} : typename E::MBuf{B + E::NC * 64, 64};
-    // SQR / MUL / SQRN serve the LDS-resident modes only; PADIC_LDS_KM calls sqr_kara_reg / mul_kara_reg on registers below
+    // SQR / MUL / SQRN serve the LDS-resident modes only; PADIC_LDS_KM / PADIC_LDS_KMR call sqr_kara_reg / mul_kara_reg on registers below
     auto SQR = [&]() {
         if constexpr (MODE == PADIC_WBUF) {
             if constexpr (NL <= PADIC_SQR_SYM_MAX_NL) E::sqr_sym_fused(A, B, nm, pm1, n0inv);
@@ -163,7 +169,8 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         const uint32_t* row = ct + (size_t)es * P.ct_words;
         // ---- digit form of ct:  sum_i  (c_i, 0) * digits(R^(i+2) mod s^2) -----------------------------
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
-        if constexpr (MODE == PADIC_LDS_KM) {
+        if constexpr (padic_reg_mode(MODE)) {
+            constexpr int RED = MODE == PADIC_LDS_KMR ? E::PADIC_KMR_RED : 0;
             // ---- table of odd powers and sliding-window schedule on register digits ----------------------------------
             // ONE loop and so one inlined copy of the squaring and of the product (each is tens of KB of straight-line
             // code): step 0 squares the base (-> slot NT), steps 1 .. NT-1 multiply by base^2 (-> slots 1 .. NT-1), then
@@ -198,8 +205,8 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
                 }
                 if (t == NT - 1) get_e = i0;             // the table is complete: start from the first window's entry
 #pragma unroll 1
-                for (int s = 0; s < nsq; ++s) E::sqr_kara_reg(a, b, nm, n0inv);
-                if (idx != 0xFF) E::mul_kara_reg(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nm, n0inv);
+                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg<RED>(a, b, nm, n0inv);
+                if (idx != 0xFF) E::template mul_kara_reg<RED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nm, n0inv);
                 if (put_e >= 0) put(put_e);
                 if (get_e >= 0) {
 #pragma unroll

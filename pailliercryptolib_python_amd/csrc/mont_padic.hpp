@@ -716,12 +716,29 @@ struct Padic {
     // w and v equal those of the row-wise sqr() / mul() exactly (the quotient digits are unique modulo R).  The difference
     // limbs depend on one operand each: after inlining, the two passes of one product share those of the left digit a and of
     // the right digit c (common subexpressions), so each is formed once per product.
+    // KRED (compile time): the quotient products sum_i mq[i] nm[k - i] of the reduction are a product of two NL-limb numbers
+    // as well, m p, and take the same column form:  Y_k = Q0_k + (Q0 + Q2 - E)_(k-H) + Q2_(k-2H),  Q0 = m0 p0, Q2 = m1 p1,
+    // E = (m0 - m1)(p0 - p1): 3 H^2 + H multiply-adds per pass (990) instead of NL^2 (1 296).  One operand is the wave-uniform
+    // modulus: its differences ndp[l] = nm[H + l] - nm[l] are H scalars.  Written with U_k = Q0_k + Q2_(k-H), ONE chain of at
+    // most H products (< H 2^58 < 2^62.2) that is stored once and kept for H columns:  Y_k = U_k + U_(k-H) - E_(k-H).
+    // The digits appear one per column, and column k needs none beyond mq[k].  For H <= k < NL the terms of the column's own
+    // digit are mq[k] nm[H] (in U_k) and mq[k] (nm[0] - nm[H]) (in -E_(k-H), from (mq[k-H] - mq[k]) ndp[0]): together mq[k] nm[0], the
+    // one product the schoolbook column has.  So the column is formed without mq[k] (its -E term takes mq[k-H] alone), mq[k]
+    // follows from it as before, mq[k] nm[0] is added, and U_k is completed with mq[k] nm[H] off the critical path; for k < H,
+    // U_k = Q0_k completed with mq[k] nm[0] is the column's last product.  -E is accumulated by signed multiply-adds onto the
+    // column: it is the schoolbook column (< NL 2^58 + 2^36 + 2^30), every partial sum is exact modulo 2^64, |partial sums of
+    // -E| < H 2^58.  mq, out and the carry are bit for bit those of the schoolbook columns.
+    // VF (compile time; all forms but KARA_MUL2): the product stream likewise as V_k = P0_k + P2_(k-H), one chain kept for H
+    // columns, X_k = V_k + V_(k-H) - D_(k-H): one stored sum and two 64-bit additions per column instead of two and four.  A
+    // square takes the pairs i < l once and doubles their sum (and that of their signed products in -D) instead of keeping
+    // doubled copies of the limbs.  Cells: tools/kara_model.py (kred, vf).
     static constexpr int KARA_SQR = 0, KARA_SQR2 = 1, KARA_MUL = 2, KARA_MUL2 = 3;
-    template <int FORM>
+    template <int FORM, bool KRED = false, bool VF = false>
     PAI_DEV static void kara_pass(uint32_t (&out)[NL], uint32_t (&mq)[NL], const uint32_t (&x)[NL], const uint32_t (&y)[NL],
                                   const uint32_t (&x2)[NL], const uint32_t (&y2)[NL], const uint32_t (&min)[NL],
                                   const uint32_t* __restrict__ nm, uint32_t n0inv) {
         static_assert(NL % 2 == 0, "even limb count");
+        static_assert(!(VF && FORM == KARA_MUL2), "the sum of two products keeps its summed half products");
         constexpr bool SYM = FORM == KARA_SQR, DBL = FORM == KARA_SQR2, SUM = FORM == KARA_MUL2;
         constexpr bool SECOND = DBL || SUM;               // - min + R p enters the reduction columns
         constexpr int H = NL / 2, NP = 2 * H - 1;         // half-product coefficients 0 .. NP - 1
@@ -753,27 +770,78 @@ struct Padic {
             return s;
         };
         uint64_t p0[NP], p2[NP];
+        uint64_t pv[H + NP];                              // VF: V_k = P0_k + P2_(k-H) of the product stream
+        uint64_t ru[H + NP];                              // KRED: U_k = Q0_k + Q2_(k-H) of the quotient stream
+        int32_t dm[H], ndp[H];                            // KRED: mq[i] - mq[H + i]; nm[H + l] - nm[l] (wave-uniform)
+        if constexpr (KRED) {
+#pragma unroll
+            for (int l = 0; l < H; ++l) ndp[l] = (int32_t)nm[H + l] - (int32_t)nm[l];
+        }
         uint64_t cc = 0, carry = 0;
 #pragma unroll
         for (int k = 0; k < 2 * NL - 1; ++k) {
             uint64_t t = 0;
             int64_t nd = 0, nd2 = 0;                      // SUM: -D_j of either pair
-            if (k < NP) { p0[k] = half(0, k); t += p0[k]; }
-            if (k >= H && k - H < NP) {
-                const int j = k - H;
-                p2[j] = half(H, j);
-                if (!SUM) t += p0[j] + p2[j];
-                const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+            if constexpr (VF && !SUM) {
+                // V_k = P0_k + P2_(k-H) as ONE chain of multiply-adds, kept for H columns: X_k = V_k + V_(k-H) - D_(k-H).
+                // A square takes the pairs i < l once and doubles their sum.
+                const bool mid = k >= H && k - H < NP;
+                uint64_t vk = 0, off = 0;
+                if (k < NP) {
+                    const int lo = k < H ? 0 : k - H + 1, hi = k < H ? k : H - 1;
 #pragma unroll
-                for (int i = lo; i <= hi; ++i) {
-                    const int l = j - i;
-                    if (SUM) { nd += (int64_t)nx[i] * (int64_t)dy[l]; nd2 += (int64_t)nx2[i] * (int64_t)dy2[l]; }
-                    else if (!SYM) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
-                    else if (i < l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy2[l]);
-                    else if (i == l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[i]);
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = k - i;
+                        if (!SYM) vk += (uint64_t)x[i] * y[l];
+                        else if (i < l) off += (uint64_t)x[i] * y[l];
+                        else if (i == l) vk += (uint64_t)x[i] * y[i];
+                    }
                 }
+                if (mid) {
+                    const int j = k - H;
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (!SYM) vk += (uint64_t)x[H + i] * y[H + l];
+                        else if (i < l) off += (uint64_t)x[H + i] * y[H + l];
+                        else if (i == l) vk += (uint64_t)x[H + i] * y[H + i];
+                    }
+                }
+                if (SYM) vk += off << 1;
+                if (k < H + NP) pv[k] = vk;
+                t = vk;
+                if (k >= H) t += pv[k - H];
+                if (mid) {
+                    const int j = k - H;
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (!SYM) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
+                        else if (i < l) nd += (int64_t)nx[i] * (int64_t)dy[l];
+                        else if (i == l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[i]);
+                    }
+                    if (SYM) t += (uint64_t)nd << 1;
+                }
+            } else {
+                if (k < NP) { p0[k] = half(0, k); t += p0[k]; }
+                if (k >= H && k - H < NP) {
+                    const int j = k - H;
+                    p2[j] = half(H, j);
+                    if (!SUM) t += p0[j] + p2[j];
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (SUM) { nd += (int64_t)nx[i] * (int64_t)dy[l]; nd2 += (int64_t)nx2[i] * (int64_t)dy2[l]; }
+                        else if (!SYM) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[l]);
+                        else if (i < l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy2[l]);
+                        else if (i == l) t += (uint64_t)((int64_t)nx[i] * (int64_t)dy[i]);
+                    }
+                }
+                if (k >= 2 * H) t += p2[k - 2 * H];
             }
-            if (k >= 2 * H) t += p2[k - 2 * H];
             uint64_t c = t + cc;
             cc = c >> RB;
             if (SUM && k >= H && k - H < NP) {
@@ -785,18 +853,70 @@ struct Padic {
             const uint64_t lowc = DBL ? (uint64_t)(((uint32_t)c & RMASK) << 1) : (uint64_t)((uint32_t)c & RMASK);
             uint64_t d = lowc;
             if (SECOND) d += k < NL ? (uint64_t)((RMASK - min[k]) + (k == 0 ? 1u : 0u)) : (uint64_t)(nm[k - NL] - (k == NL ? 1u : 0u));
-            const int lo = k < NL ? 0 : k - NL + 1, hi = k < NL ? k - 1 : NL - 1;
-            // the quotient products that do not wait for the previous column, then its carry and newest digit
+            if constexpr (KRED) {
+                // quotient products m p by Karatsuba columns (see above).  U_k = Q0_k + Q2_(k-H) is ONE chain of multiply-adds,
+                // kept for H columns; the column is U_k + U_(k-H) - E_(k-H).  The terms of the newest known digit mq[k - 1]
+                // close their chains; the column's own digit mq[k] is taken from the column without its terms.
+                constexpr int NU = H + NP;                // U_0 .. U_(NU-1)
+                const bool has_u = k < NU, mid = k >= H && k - H < NP;
+                uint64_t u = 0;
+                if (k < NP) {
+                    const int lo0 = k < H ? 0 : k - H + 1, hi0 = k < H ? k - 1 : H - 1;
 #pragma unroll
-            for (int i = lo; i <= hi; ++i)
-                if (i != k - 1) d += (uint64_t)mq[i] * nm[k - i];
-            d += carry;
-            if (k >= 1 && k - 1 < NL) d += (uint64_t)mq[k - 1] * nm[1];
-            if (k < NL) {
-                mq[k] = ((uint32_t)d * n0inv) & RMASK;
-                d += (uint64_t)mq[k] * nm[0];
+                    for (int i = lo0; i <= hi0; ++i)
+                        if (i != k - 1) u += (uint64_t)mq[i] * nm[k - i];
+                }
+                if (mid) {
+                    const int j = k - H;
+                    const int lo2 = j < H ? 0 : j - H + 1, hi2 = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo2; i <= hi2; ++i) {
+                        const int l = j - i;
+                        if (i == j && k < NL) {           // mq[k] unknown: the share of mq[j] alone; mq[k] (nm[H] - ndp[0]) = mq[k] nm[0] follows
+                            d += (uint64_t)((int64_t)(int32_t)mq[i] * (int64_t)ndp[0]);
+                        } else if (H + i != k - 1) {
+                            u += (uint64_t)mq[H + i] * nm[H + l];
+                            d += (uint64_t)((int64_t)dm[i] * (int64_t)ndp[l]);
+                        }
+                    }
+                }
+                if (k >= H) d += ru[k - H];
+                d += carry;
+                if (k >= 1 && k <= H) u += (uint64_t)mq[k - 1] * nm[1];
+                if (k - 1 >= H && k - 1 < NL) {           // i = j - 1, l = 1
+                    u += (uint64_t)mq[k - 1] * nm[H + 1];
+                    d += (uint64_t)((int64_t)dm[k - 1 - H] * (int64_t)ndp[1]);
+                }
+                if (k < H) {
+                    mq[k] = (((uint32_t)d + (uint32_t)u) * n0inv) & RMASK;
+                    u += (uint64_t)mq[k] * nm[0];
+                    d += u;
+                } else {
+                    if (has_u) d += u;
+                    if (k < NL) {
+                        mq[k] = ((uint32_t)d * n0inv) & RMASK;
+                        d += (uint64_t)mq[k] * nm[0];
+                        u += (uint64_t)mq[k] * nm[H];
+                        dm[k - H] = (int32_t)mq[k - H] - (int32_t)mq[k];
+                    } else {
+                        out[k - NL] = (uint32_t)d & RMASK;
+                    }
+                }
+                if (has_u) ru[k] = u;
             } else {
-                out[k - NL] = (uint32_t)d & RMASK;
+                const int lo = k < NL ? 0 : k - NL + 1, hi = k < NL ? k - 1 : NL - 1;
+                // the quotient products that do not wait for the previous column, then its carry and newest digit
+#pragma unroll
+                for (int i = lo; i <= hi; ++i)
+                    if (i != k - 1) d += (uint64_t)mq[i] * nm[k - i];
+                d += carry;
+                if (k >= 1 && k - 1 < NL) d += (uint64_t)mq[k - 1] * nm[1];
+                if (k < NL) {
+                    mq[k] = ((uint32_t)d * n0inv) & RMASK;
+                    d += (uint64_t)mq[k] * nm[0];
+                } else {
+                    out[k - NL] = (uint32_t)d & RMASK;
+                }
             }
             carry = d >> RB;
         }
@@ -824,18 +944,26 @@ struct Padic {
         wave_lds_fence();
     }
     // ---- the same on digits that STAY in registers from one operation to the next (kernels_padic.hpp: PADIC_LDS_KM) -----
+    // RED (compile time): bit FORM set = that pass takes its quotient products by Karatsuba columns (kara_pass<FORM, true>);
+    // KRED_VF = the product streams of the squaring's two passes in the one-chain form V_k, KRED_VFM = that of a product's
+    // first pass (the second, a sum of two products, keeps its summed half products and the 128-bit middle cell)
+    static constexpr int KRED_VF = 16, KRED_VFM = 32;
+    static constexpr int PADIC_KMR_RED = (1 << KARA_SQR) | (1 << KARA_SQR2) | (1 << KARA_MUL) | KRED_VF | KRED_VFM;
+    static constexpr bool kred(int RED, int FORM) { return (RED >> FORM) & 1; }
     // (a, b) <- (a, b)^2
+    template <int RED = 0>
     PAI_DEV static void sqr_kara_reg(uint32_t (&a)[NL], uint32_t (&b)[NL], const uint32_t* __restrict__ nm, uint32_t n0inv) {
+        constexpr bool VF = (RED & KRED_VF) != 0;
         uint32_t m[NL], w[NL], m2[NL], v[NL];
-        kara_pass<KARA_SQR>(w, m, a, a, a, a, m, nm, n0inv);
-        kara_pass<KARA_SQR2>(v, m2, a, b, a, b, m, nm, n0inv);
+        kara_pass<KARA_SQR, kred(RED, KARA_SQR), VF>(w, m, a, a, a, a, m, nm, n0inv);
+        kara_pass<KARA_SQR2, kred(RED, KARA_SQR2), VF>(v, m2, a, b, a, b, m, nm, n0inv);
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }
     // (a, b) <- (a, b) * (c, d): w = (a c + m p) / R, v = (a d + b c - m + R p + m' p) / R, 3 H^2 + 6 H^2 + 2 NL^2 limb
     // products (5 508 at 36 limbs) instead of the row-wise 5 NL^2 (6 480).  rsrc(g, ch): chunk ch of the right operand's
     // digit g (0 = c, 1 = d), each chunk loaded once; d is fetched behind the first pass.
-    template <class RSrc>
+    template <int RED = 0, class RSrc>
     PAI_DEV static void mul_kara_reg(uint32_t (&a)[NL], uint32_t (&b)[NL], RSrc&& rsrc, const uint32_t* __restrict__ nm,
                                      uint32_t n0inv) {
         uint32_t c[NL], d[NL], m[NL], w[NL], m2[NL], v[NL];
@@ -844,13 +972,13 @@ struct Padic {
             const uint4 t = rsrc(0, ch);
             c[4 * ch] = t.x; c[4 * ch + 1] = t.y; c[4 * ch + 2] = t.z; c[4 * ch + 3] = t.w;
         }
-        kara_pass<KARA_MUL>(w, m, a, c, a, c, m, nm, n0inv);
+        kara_pass<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0>(w, m, a, c, a, c, m, nm, n0inv);
 #pragma unroll
         for (int ch = 0; ch < NC; ++ch) {
             const uint4 t = rsrc(1, ch);
             d[4 * ch] = t.x; d[4 * ch + 1] = t.y; d[4 * ch + 2] = t.z; d[4 * ch + 3] = t.w;
         }
-        kara_pass<KARA_MUL2>(v, m2, a, d, b, c, m, nm, n0inv);
+        kara_pass<KARA_MUL2, kred(RED, KARA_MUL2)>(v, m2, a, d, b, c, m, nm, n0inv);
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }

@@ -382,6 +382,7 @@ struct ScopedKernelTimer {
 //   PAI_DISABLE="padic,pair,..."   engines / forms to leave out: padic (digit-pair engines: lane-group and wide fallbacks
 //                                  serve), pair, pair_ctmul, wide, gform (plain fixed-base tables), fb_chain, lat_dense, lat_enc_m1, lat_add_m1
 //                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns),
+//                                  padic_kara_red (36-limb decrypt: quotient products of the Montgomery reductions schoolbook, kernel mode PADIC_LDS_KM),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,

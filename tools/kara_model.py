@@ -8,6 +8,14 @@ value and records the largest one, and it asserts that
   - X_k (accumulated modulo 2^64) equals the schoolbook column sum_i x_i y_(k-i) exactly,
   - cc, d and the carries never reach 2^64,
   - w = (a^2 + m p) / R and v = (2 a b - m + R p + m' p) / R exactly, and w + v p == (a + b p)^2 R^-1 (mod p^2),
+  - with kred (kara_pass<FORM, true>): the quotient products m p of the reduction by the same column form,
+    Y_k = Q0_k + (Q0 + Q2 - E)_(k-H) + Q2_(k-2H) = U_k + U_(k-H) - E_(k-H) with U_k = Q0_k + Q2_(k-H), Q0 = m0 p0,
+    Q2 = m1 p1, E = (m0 - m1)(p0 - p1): the stored sums U_k (one chain of at most H products each) fit 64 bits, every signed product and every partial sum of -E fits int64, the reduction column d (exact modulo
+    2^64 at every partial sum) ends as the schoolbook column in [0, 2^64), and the quotient digits, out and the carry are
+    those of the schoolbook rule; the multiply-adds of the reduction are counted (3 H^2 + H instead of NL^2),
+  - with vf (kara_pass<FORM, KRED, true>; not for MUL2): the product stream as V_k = P0_k + P2_(k-H), one chain kept for H
+    columns, X_k = V_k + V_(k-H) - D_(k-H); a square sums the pairs i < l once and doubles the sum (likewise their signed
+    products in -D): the chains, the doubled sums and V_k fit 64 bits resp. int64, X_k is the schoolbook column,
   - for a product: the summed half products of a d + b c fit 64 bits, their signed difference part fits int64, the middle
     part is non-negative and enters through a 128-bit cell, and w, v are those of the row-wise product rule.
 Run: python tools/kara_model.py [rounds]
@@ -32,12 +40,18 @@ def value(l):
 class Stats:
     def __init__(self):
         self.max_cc = self.max_d = self.max_col = self.max_run = self.max_e = 0
+        self.max_rq = self.max_red_e = 0      # kred: largest stored half product, largest |partial sum of -E|
+        self.red_macs = 0                     # multiply-adds of the quotient products in the last pass
+        self.dm_signs = set()                 # kred: signs of mq[i] - mq[H + i] met
 
 
 SQR, SQR2, MUL, MUL2 = 0, 1, 2, 3     # kara_pass<FORM>: KARA_SQR, KARA_SQR2, KARA_MUL, KARA_MUL2
+VF = 16                               # sqr_kara_reg<RED>: the squaring's product streams in the one-chain form V_k
+VFM = 32                              # mul_kara_reg<RED>: the same for the first pass of a product (a c)
+KMR_RED = 1 << SQR | 1 << SQR2 | 1 << MUL | VF | VFM      # Padic::PADIC_KMR_RED: what kernel mode PADIC_LDS_KMR runs
 
 
-def kara_pass(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None):
+def kara_pass(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False):
     """One pass of kara_pass<FORM>; x, y (x2, y2: the second pair of MUL2), mnin, nm are limb lists.  Returns (out limbs,
     quotient limbs).  form may be given as False / True for the two squaring passes."""
     form = int(form)
@@ -77,17 +91,64 @@ def kara_pass(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None):
 
     p0 = [0] * NP
     p2 = [0] * NP
+    pv = [0] * (H + NP)  # vf: V_k = P0_k + P2_(k-H) of the product stream
     cc = carry = 0
     mq = [0] * NL
     out = [0] * NL
+    ru = [0] * (H + NP)  # kred: U_k = Q0_k + Q2_(k-H) of the quotient stream, live for H columns each
+    dm = [0] * H         # kred: mq[i] - mq[H + i]
+    ndp = [nm[H + l] - nm[l] for l in range(H)]
+    macs = 0
     for k in range(2 * NL - 1):
         t = 0            # unbounded running value; the cell holds t mod 2^64
         nd = [0, 0]      # MUL2: -D_j of either pair, two signed 64-bit cells (their sum can pass 2^63)
         mid = H <= k < H + NP
-        if k < NP:
+        if vf and not summ:
+            # V_k = P0_k + P2_(k-H) as one chain, kept for H columns: X_k = V_k + V_(k-H) - D_(k-H); a square takes the
+            # pairs i < l once and doubles their sum (off), likewise in -D (ndo)
+            vk = off = ndo = 0
+            for o, jj, on in ((0, k, k < NP), (H, k - H, mid)):
+                if not on:
+                    continue
+                lo, hi = (0, jj) if jj < H else (jj - H + 1, H - 1)
+                for i in range(lo, hi + 1):
+                    l = jj - i
+                    if not sym:
+                        vk += x[o + i] * y[o + l]
+                    elif i < l:
+                        off += x[o + i] * y[o + l]
+                    elif i == l:
+                        vk += x[o + i] * y[o + i]
+                    assert vk <= M64 and off <= M64, "chain of half products wraps"
+            if sym:
+                assert off << 1 <= M64
+                vk += off << 1
+            assert vk <= M64, "V_k wraps"
+            st.max_run = max(st.max_run, vk)
+            if k < H + NP:
+                pv[k] = vk
+            else:
+                assert vk == 0
+            t = vk + (pv[k - H] if k >= H else 0)
+            if mid:
+                j = k - H
+                lo, hi = (0, j) if j < H else (j - H + 1, H - 1)
+                for i in range(lo, hi + 1):
+                    l = j - i
+                    pr = nx[i] * dy[l]
+                    assert -(1 << 63) <= pr < (1 << 63), "signed product leaves int64"
+                    if not sym:
+                        t += pr
+                    elif i < l:
+                        ndo += pr
+                        assert -(1 << 62) <= ndo < (1 << 62), "signed sum of the pairs i < l does not double in int64"
+                    elif i == l:
+                        t += pr
+                t += ndo << 1
+        elif k < NP:
             p0[k] = half(0, k)
             t += p0[k]
-        if mid:
+        if mid and not (vf and not summ):
             j = k - H
             p2[j] = half(H, j)
             if not summ:
@@ -113,7 +174,7 @@ def kara_pass(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None):
                 assert -(1 << 63) <= pr < (1 << 63), "signed product leaves int64"
                 t += pr
                 st.max_run = max(st.max_run, t)
-        if k >= 2 * H:
+        if k >= 2 * H and not (vf and not summ):
             t += p2[k - 2 * H]
         # the cell is exact modulo 2^64; the column itself must be the schoolbook one and lie in [0, 2^64)
         want = column(x, y, k) + (column(x2, y2, k) if summ else 0)
@@ -141,36 +202,113 @@ def kara_pass(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None):
         if second:
             d += (MASK - mnin[k]) + (1 if k == 0 else 0) if k < NL else nm[k - NL] - (1 if k == NL else 0)
         lo, hi = (0, k - 1) if k < NL else (k - NL + 1, NL - 1)
-        for i in range(lo, hi + 1):
-            if i != k - 1:
-                d += mq[i] * nm[k - i]
-        d += carry
-        if 1 <= k and k - 1 < NL:
-            d += mq[k - 1] * nm[1]
-        if k < NL:
-            mq[k] = ((d & 0xFFFFFFFF) * n0inv) & MASK
-            d += mq[k] * nm[0]
+        # the schoolbook column up to (not including) the column's own digit
+        school = d + carry + sum(mq[i] * nm[k - i] for i in range(lo, hi + 1))
+        if not kred:
+            macs += hi - lo + 1 + (1 if k < NL else 0)
+            d = school
+            if k < NL:
+                mq[k] = ((d & 0xFFFFFFFF) * n0inv) & MASK
+                d += mq[k] * nm[0]
+            else:
+                out[k - NL] = d & MASK
         else:
-            out[k - NL] = d & MASK
+            # d is the 64-bit cell (exact modulo 2^64 at every partial sum: signed terms); dt its unbounded value
+            dt = d
+            has_u, midr = k < H + NP, H <= k < H + NP
+            u = 0                                           # U_k = Q0_k + Q2_(k-H): one chain of multiply-adds
+            e = 0                                           # partial sum of -E_j (chained onto d in the kernel)
+
+            def signed(a, b):
+                nonlocal dt, e, macs
+                assert -(1 << 31) <= a < (1 << 31) and -(1 << 31) <= b < (1 << 31), "signed operand leaves int32"
+                pr = a * b
+                assert -(1 << 63) <= pr < (1 << 63), "signed product leaves int64"
+                e += pr
+                assert -(1 << 63) <= e < (1 << 63), "partial sum of -E leaves int64"
+                st.max_red_e = max(st.max_red_e, abs(e))
+                dt += pr
+                macs += 1
+
+            if k < NP:
+                lo0, hi0 = (0, k - 1) if k < H else (k - H + 1, H - 1)
+                for i in range(lo0, hi0 + 1):
+                    if i != k - 1:
+                        u += mq[i] * nm[k - i]
+                        macs += 1
+            if midr:
+                j = k - H
+                lo2, hi2 = (0, j) if j < H else (j - H + 1, H - 1)
+                for i in range(lo2, hi2 + 1):
+                    l = j - i
+                    if i == j and k < NL:
+                        signed(mq[i], ndp[0])
+                    elif H + i != k - 1:
+                        u += mq[H + i] * nm[H + l]
+                        macs += 1
+                        signed(dm[i], ndp[l])
+            if k >= H:
+                dt += ru[k - H]
+            dt += carry
+            if 1 <= k <= H:
+                u += mq[k - 1] * nm[1]
+                macs += 1
+            if H <= k - 1 < NL:
+                u += mq[k - 1] * nm[H + 1]
+                macs += 1
+                signed(dm[k - 1 - H], ndp[1])
+            if k < H:
+                mq[k] = ((((dt & 0xFFFFFFFF) + (u & 0xFFFFFFFF)) & 0xFFFFFFFF) * n0inv) & MASK
+                u += mq[k] * nm[0]
+                macs += 1
+                dt += u
+            else:
+                if has_u:
+                    dt += u
+                if k < NL:
+                    assert dt == school, (k, dt, school)      # all but the own digit: m[k] (p[H] - (p[H] - p[0])) follows
+                    mq[k] = ((dt & 0xFFFFFFFF) * n0inv) & MASK
+                    dt += mq[k] * nm[0]
+                    u += mq[k] * nm[H]
+                    macs += 2
+                    dm[k - H] = mq[k - H] - mq[k]
+                    assert -(1 << 31) <= dm[k - H] < (1 << 31)
+                    st.dm_signs.add((dm[k - H] > 0) - (dm[k - H] < 0))
+                else:
+                    out[k - NL] = dt & MASK
+            assert u <= M64, "stored sum of half products of the quotient stream wraps"
+            st.max_rq = max(st.max_rq, u)
+            if has_u:
+                ru[k] = u
+            else:
+                assert u == 0
+            # the cell is the schoolbook column: same digit, same value, inside [0, 2^64)
+            want_d = school + (mq[k] * nm[0] if k < NL else 0)
+            assert dt == want_d and 0 <= dt <= M64, (k, dt, want_d)
+            if k < NL:
+                assert mq[k] == ((school & 0xFFFFFFFF) * n0inv) & MASK
+            d = dt
         assert d <= M64, "reduction column wraps"
         st.max_d = max(st.max_d, d)
         carry = d >> RB
     top = carry + (cc << 1 if dbl else cc) + (nm[NL - 1] if second else 0)
     assert top <= 0xFFFFFFFF
+    st.red_macs = macs
     out[NL - 1] = top          # unmasked here: the caller checks that it fits 29 bits where the digits are in range
     return out, mq
 
 
-def mul_kara(a, b, c, d, p, NL, st, in_range=True):
-    """(a, b) * (c, d) -> (w, v) by the two product passes (mul_kara_reg); checks them against the row-wise product rule
+def mul_kara(a, b, c, d, p, NL, st, in_range=True, red=0):
+    """(a, b) * (c, d) -> (w, v) by the two product passes (mul_kara_reg<red>: bit FORM of red = that pass reduces by
+    Karatsuba columns); checks them against the row-wise product rule
     w = (a c + m p) / R, v = (a d + b c - m + R p + m' p) / R on Python integers (m, m' the unique quotients modulo R)."""
     R = 1 << (RB * NL)
     nm = limbs(p, NL)
     n0inv = (-pow(p, -1, B)) % B
     al, bl, cl, dl = limbs(a, NL), limbs(b, NL), limbs(c, NL), limbs(d, NL)
     assert (value(al), value(bl), value(cl), value(dl)) == (a, b, c, d)
-    w, m = kara_pass(MUL, al, cl, [0] * NL, nm, n0inv, st)
-    v, m2 = kara_pass(MUL2, al, dl, m, nm, n0inv, st, x2=bl, y2=cl)
+    w, m = kara_pass(MUL, al, cl, [0] * NL, nm, n0inv, st, kred=bool(red >> MUL & 1), vf=bool(red & VFM))
+    v, m2 = kara_pass(MUL2, al, dl, m, nm, n0inv, st, x2=bl, y2=cl, kred=bool(red >> MUL2 & 1))
     W, M, V, M2 = value(w), value(m), value(v), value(m2)
     pinv = pow(p, -1, R)
     assert M == (-a * c * pinv) % R and W == (a * c + M * p) // R and (a * c + M * p) % R == 0
@@ -183,15 +321,15 @@ def mul_kara(a, b, c, d, p, NL, st, in_range=True):
     return W, V
 
 
-def sqr_kara(a, b, p, NL, st, in_range=True):
-    """(a, b) -> (w, v) by the two passes; checks the exact relations."""
+def sqr_kara(a, b, p, NL, st, in_range=True, red=0):
+    """(a, b) -> (w, v) by the two passes (sqr_kara_reg<red>); checks the exact relations."""
     R = 1 << (RB * NL)
     nm = limbs(p, NL)
     n0inv = (-pow(p, -1, B)) % B
     al, bl = limbs(a, NL), limbs(b, NL)
     assert value(al) == a and value(bl) == b
-    w, m = kara_pass(False, al, al, [0] * NL, nm, n0inv, st)
-    v, m2 = kara_pass(True, al, bl, m, nm, n0inv, st)
+    w, m = kara_pass(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF))
+    v, m2 = kara_pass(SQR2, al, bl, m, nm, n0inv, st, kred=bool(red >> SQR2 & 1), vf=bool(red & VF))
     W, M, V, M2 = value(w), value(m), value(v), value(m2)
     assert (a * a + M * p) % R == 0 and W == (a * a + M * p) // R
     assert V * R == 2 * a * b - M + R * p + M2 * p
@@ -227,7 +365,7 @@ def corners(p, NL, rng):
     return out
 
 
-def run(rounds=2, seed=1):
+def run(rounds=2, seed=1, red=0):
     rng = random.Random(seed)
     st = Stats()
     for bits, NL in ((1024, 36), (1000, 36), (600, 24)):
@@ -235,25 +373,29 @@ def run(rounds=2, seed=1):
             p = random_prime(bits, rng)
             cs = corners(p, NL, rng)
             for a, b, ok in cs:
-                sqr_kara(a, b, p, NL, st, in_range=ok)
+                sqr_kara(a, b, p, NL, st, in_range=ok, red=red)
             for i, (a, b, ok) in enumerate(cs):          # products: every corner against itself, its neighbour, its mirror
                 for c, d, ok2 in (cs[i], cs[(i + 1) % len(cs)], (b, a, ok)):
-                    mul_kara(a, b, c, d, p, NL, st, in_range=ok and ok2)
+                    mul_kara(a, b, c, d, p, NL, st, in_range=ok and ok2, red=red)
         # a run of squarings stays inside the lazy bound
         p = random_prime(bits, rng)
         a, b = rng.randrange(2 * p), rng.randrange(2 * p)
         for _ in range(8):
-            a, b = sqr_kara(a, b, p, NL, st)
+            a, b = sqr_kara(a, b, p, NL, st, red=red)
             assert a < 2 * p + (p >> 18) and b < 2 * p + (p >> 18)
         # ... and so does a run of products by a fixed element (the table build)
         c, d = rng.randrange(2 * p), rng.randrange(2 * p)
         for _ in range(8):
-            a, b = mul_kara(a, b, c, d, p, NL, st)
+            a, b = mul_kara(a, b, c, d, p, NL, st, red=red)
             assert a < 2 * p + (p >> 18) and b < 2 * p + (p >> 18)
     return st
 
 
 if __name__ == "__main__":
-    s = run(int(sys.argv[1]) if len(sys.argv) > 1 else 2)
+    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+    s = run(rounds)
+    run(rounds, red=KMR_RED)
+    r = run(rounds, red=15 | VF | VFM)
+    print({"red_max_rq_log2": r.max_rq.bit_length(), "red_max_e_log2": r.max_red_e.bit_length(), "red_max_d_log2": r.max_d.bit_length()})
     print({"max_col_log2": s.max_col.bit_length(), "max_cc_log2": s.max_cc.bit_length(),
            "max_d_log2": s.max_d.bit_length(), "max_running_log2": s.max_run.bit_length(), "max_mid_cell_log2": s.max_e.bit_length()})
