@@ -196,7 +196,9 @@ PAI_DEV void unpack_row(uint32_t (&x)[G::NLL], const uint32_t* stage) {
 }
 
 // limb slices (canonical 29-bit limbs) -> packed u32 words of one element, staged through LDS
-// (buffer `lds` of G::LDS_WORDS words, layout [limb][element]).  Bits above 32*W32 must be zero.
+// (buffer `lds` of G::LDS_WORDS words, layout [limb][element]).  Bits above 32*W32 must be zero.  A row may be wider than the
+// geometry (2 * words(key_bits) words against 29 NL bits: n of 521 bits has rows of 34 words on 36 limbs): the words that start
+// above the top limb are zero, not whatever lies behind the operand buffer.
 template <class G>
 PAI_DEV void store_elem(const uint32_t (&x)[G::NLL], uint32_t* __restrict__ row, int W32, uint32_t* lds) {
     const int t = G::gl(), e = G::elem();
@@ -207,7 +209,7 @@ PAI_DEV void store_elem(const uint32_t (&x)[G::NLL], uint32_t* __restrict__ row,
     for (int k = t; k < W32; k += G::T) {
         const int j0 = (32 * k) / RB;
         const int s0 = 32 * k - RB * j0;
-        uint64_t v = (uint64_t)lds[j0 * G::EPB + e] >> s0;
+        uint64_t v = j0 < G::NL ? (uint64_t)lds[j0 * G::EPB + e] >> s0 : 0;
         if (j0 + 1 < G::NL) v |= (uint64_t)lds[(j0 + 1) * G::EPB + e] << (RB - s0);
         if (j0 + 2 < G::NL) v |= (uint64_t)lds[(j0 + 2) * G::EPB + e] << (2 * RB - s0);
         row[k] = (uint32_t)v;

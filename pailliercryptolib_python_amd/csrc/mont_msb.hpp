@@ -15,10 +15,15 @@
 //     the accumulator proper is < 2 Mt < 2^(P+1): the digit estimate (computed modulo 2^64 from cells whose weights it knows)
 //     never sees it, the slide drops it, and the final carry sweep masks it off the top limb.
 //   * q^ is never above the true digit (all roundings go down; a window that reads negative because the lazy columns below
-//     it still hold the carries gives 0) and at most 1 below it: by induction 0 <= acc < 2 Mt (then acc B + a b_i <
-//     (2 B + 4) Mt for any a of the row's word size, off >= 1; V < 2^62 (1 + 2^-28), and the roundings — mu's, < V / 2^63, the
-//     columns left out, < 2^-24 — stay below 0.51), so q^ <= 2 B + 4 and a column gains < 3 x 2^58 per row: up to 20 rows
-//     between carry normalisations (Montgomery rows: 24).  A normalisation runs BEFORE the hand-over to the next lane and
+//     it still hold the carries gives 0) and at most 1 below it: by induction 0 <= acc < 2 Mt.  The multiplicand is ANY word
+//     pattern of the row, and build_msb_ctx admits rows of up to bits(M) + 2 bits: a < 2^(bits + 2) <= 8 M (8 M itself only for the
+//     smallest modulus of a bit length), so with off >= 1 a b_i < 8 M B <= 8 Mt and acc B + a b_i < (2 B + 8) Mt; V < 2^62 (1 + 2^-27),
+//     and the roundings — mu's, < V / 2^63, the columns left out, < 2^-24 — stay below 0.51, so q^ <= 2 B + 8.  A column gains
+//     a_j b_i < 2^58 and q^ w_j < (2 B + 8) B = 2^59 + 2^32 per row, < 3 x 2^58 + 2^32: 20 rows between carry normalisations
+//     (Montgomery rows: 24) add < 60 x 2^58 + 2^37 to the < 2^36 a normalisation leaves, against the cell's 64 x 2^58 — a margin of
+//     4 x 2^58, one row's worth.  (For residues a < M the same sum is 2 B + 1 and the margin the same row: the budget is set by
+//     q^ w_j, not by the operand's excess.)  tools/msb_model.py asserts q^ <= 2 B + 8 and that no cell wraps, on rows of bits(M) + 2
+//     bits at the smallest moduli.  A normalisation runs BEFORE the hand-over to the next lane and
 //     splits the top cell too, so that the cell the next lane receives is as small as its own.
 //   * V needs the top FOUR cells (the lazy carries of the fourth still weigh 2^(35-29-tb+32) quotient units / 2^32).
 #pragma once

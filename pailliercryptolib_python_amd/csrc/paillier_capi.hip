@@ -307,8 +307,9 @@ struct ModSetup {
 
 // Constants of the most-significant-limb-first product (mont_msb.hpp) for modulus M on geometry g and rows of w32 words, or
 // nullptr where its conditions do not hold: a lane-group geometry with the estimate's four cells in one lane, M's top limb at
-// least one limb below the geometry's (off >= 1: the products a b_i then stay below 4 Mt for ANY word pattern of the row), 3 .. 26
-// bits of M in its top limb, rows no wider than the limbs the multiplier is read from.
+// least one limb below the geometry's (off >= 1: the products a b_i then stay below 8 Mt for ANY word pattern of the row), 3 .. 26
+// bits of M in its top limb, rows no wider than the limbs the multiplier is read from and than bits(M) + 2 bits (a < 8 M: the
+// operand range of the bound written in mont_msb.hpp).
 static MsbCtx* build_msb_ctx(const Limbs& M, const GeoOps* g, int w32) {
     if (!g || !g->modmul_msb || g->t > 8 || g->nll < 4) return nullptr;
     const int NL = g->nl, bits = hbn::bitlen(M);

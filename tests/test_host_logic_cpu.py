@@ -82,7 +82,11 @@ def test_msb_first_product_model_bounds():
         # (n^2 of the `zeros` keys is one bit short of 2 key bits)
         extreme = [(p_ * q_) ** 2 for _, f, b, p_, q_ in load_extreme_keys() if 2 * b == key and f in ("ones", "zeros", "n0", "n0_one")]
         assert len(extreme) == 4
-        for M in [mm.rand_modulus(2 * key, rng), (1 << (2 * key)) - 1 - 2 * rng.getrandbits(40), (1 << (2 * key - 1)) + 1 + 2 * rng.getrandbits(40)] + extreme:
+        # ... and the smallest modulus whose rows the context still admits (csrc/paillier_capi.hip: build_msb_ctx, rows of bits(M) + 2
+        # bits): `full` below is then just under 8 M, the operand range the bound in csrc/mont_msb.hpp is written for
+        widest_rows = (1 << (2 * key - 3)) + 1 + 2 * rng.getrandbits(40)
+        for M in [mm.rand_modulus(2 * key, rng), (1 << (2 * key)) - 1 - 2 * rng.getrandbits(40), (1 << (2 * key - 1)) + 1 + 2 * rng.getrandbits(40),
+                  widest_rows] + extreme:
             p = mm.Params(M, NLL, T, U)
             assert p.ok
             full = (1 << (2 * key)) - 1
@@ -90,7 +94,8 @@ def test_msb_first_product_model_bounds():
             stats = {}
             for a, b in ((M - 1, M - 1), (1, 1), (0, 5), (full, full), (ones, ones), (rng.randrange(M), rng.randrange(M)), (full, rng.getrandbits(2 * key))):
                 assert mm.msb_mul(p, a, b, stats) == a * b % M
-            assert set(stats) <= {0, 1, "qmax"}
+            assert set(stats) <= {0, 1, "qmax"} and stats["qmax"] <= 2 * mm.B + 8
+            assert M != widest_rows or 4 * M < full < 8 * M
     # the corners of the context's conditions (csrc/paillier_capi.hip: build_msb_ctx): 3 and 26 bits of the modulus in its top limb,
     # shifted up by 1 and by 16 limbs, smallest and largest modulus of the bit length
     for NLL, T, U in ((36, 4, 6), (28, 8, 4)):

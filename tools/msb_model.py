@@ -70,6 +70,7 @@ def msb_mul(p, a, b, stats=None):
                 q = 0
             q_true = A_true // p.Mt
             assert q <= q_true, ("overestimate", q, q_true)
+            assert q <= 2 * B + 8, ("digit above the bound of csrc/mont_msb.hpp", q)      # a < 8 M, off >= 1: acc B + a b_i < (2 B + 8) Mt
             assert q >= q_true - 1, ("underestimate", q, q_true)
             if stats is not None:
                 stats[q_true - q] = stats.get(q_true - q, 0) + 1
@@ -156,6 +157,8 @@ if __name__ == "__main__":
                 M = (1 << (2 * key)) - 1 - 2 * rng.getrandbits(40)
             if it == 2:
                 M = (1 << (2 * key - 1)) + 1 + 2 * rng.getrandbits(40)
+            if it == 3:                                   # the smallest modulus whose rows build_msb_ctx still admits: rows of bits(M) + 2 bits, up to 8 M
+                M = (1 << (2 * key - 3)) + 1 + 2 * rng.getrandbits(40)
             p = Params(M, NLL, T, U)
             assert p.ok, (key, p.tb)
             cases = [(M - 1, M - 1), (1, 1), (0, 5), (M - 1, 1), (1, M - 1), (M - 1, (1 << (2 * key - 3)) - 1),
