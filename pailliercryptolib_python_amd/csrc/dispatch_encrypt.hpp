@@ -234,8 +234,10 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
             t.stop();
         } else {
             pk->table.ensure(g->table_words((size_t)grid) * 4);
+            ScopedKernelTimer t("k_pow(r^n)", s, "lane_group");
             g->modexp_fixed(s, grid, pk->msq.d_ctx, d_r, pk->n_words, pk->d_nexp, pk->n_words, hbn::bitlen(pk->n),
                             pk->tmp.as<uint32_t>(), pk->ct_words, (int)N, pk->table.as<uint32_t>(), 0);
+            t.stop();
         }
         g->encrypt(s, grid, P, d_m, pk->tmp.as<uint32_t>(), d_ct_in, d_ct_out, (int)N, from_plain ? 3 : 4);
     }

@@ -126,3 +126,26 @@ def djn_obfuscate_many(key, cts, rs):
     """[orc.apply_obfuscator(key, c, r)]: c hs^r mod n^2."""
     obf = pow_many([key.hs] * len(cts), rs, key.nsq)
     return [c * o % key.nsq for c, o in zip(cts, obf)]
+
+
+# ---- the model of the packed-plaintext format (include/paillier_hip.h, "packed ciphertexts"), Python ints only ----------------
+def model_max_slots(n_bits, b):
+    return (n_bits - 2) // b
+
+
+def model_bias(b, k):
+    return sum(1 << (b * j + b - 1) for j in range(k))
+
+
+def model_pack(mantissas, b, k, n):
+    assert all(-(1 << (b - 1)) <= m < (1 << (b - 1)) for m in mantissas)
+    return [sum(m << (b * j) for j, m in enumerate(mantissas[g:g + k])) % n for g in range(0, len(mantissas), k)]
+
+
+def model_unpack(residue, b, k, n):
+    if residue >= n:
+        return 2, None
+    q = (residue + model_bias(b, k)) % n
+    if q >= 1 << (k * b):
+        return 1, None
+    return 0, [((q >> (b * j)) & ((1 << b) - 1)) - (1 << (b - 1)) for j in range(k)]

@@ -24,7 +24,7 @@ from pailliercryptolib_python_amd import PaillierPackedNumber, PaillierPrivateKe
 from pailliercryptolib_python_amd.bindings import ipclCipherText, ipclPublicKey
 from pailliercryptolib_python_amd.paillier import PaillierEncryptedNumber
 
-from ._util import disable, pow_many, rand_below, tune
+from ._util import disable, model_bias, model_max_slots, model_pack, model_unpack, pow_many, rand_below, tune
 
 pytestmark = pytest.mark.gpu
 
@@ -41,29 +41,7 @@ def keypair(bits):
     return _KEYS[bits]
 
 
-# ---- the model of the format (Python ints only) -----------------------------------------------------------------------------
-def model_max_slots(n_bits, b):
-    return (n_bits - 2) // b
-
-
-def model_bias(b, k):
-    return sum(1 << (b * j + b - 1) for j in range(k))
-
-
-def model_pack(mantissas, b, k, n):
-    assert all(-(1 << (b - 1)) <= m < (1 << (b - 1)) for m in mantissas)
-    return [sum(m << (b * j) for j, m in enumerate(mantissas[g:g + k])) % n for g in range(0, len(mantissas), k)]
-
-
-def model_unpack(residue, b, k, n):
-    if residue >= n:
-        return 2, None
-    q = (residue + model_bias(b, k)) % n
-    if q >= 1 << (k * b):
-        return 1, None
-    return 0, [((q >> (b * j)) & ((1 << b) - 1)) - (1 << (b - 1)) for j in range(k)]
-
-
+# ---- the model of the format (Python ints only): model_max_slots, model_bias, model_pack and model_unpack live in tests/_util.py ----
 def model_mantissa(x, E):
     """rint(x 2^E), ties to even, exactly (Fraction.__round__ rounds half to even); ints: x << E"""
     return round(Fraction(x) * Fraction(2) ** E) if isinstance(x, float) else int(x) << E

@@ -325,6 +325,72 @@ def test_ct_invert_other_key_sizes():
         assert limbs_to_ints(out.get()) == [pow(x, -1, key.nsq) for x in a]
 
 
+INVERT_DIRECT_KEYS = ["seeded-1024", "bench-2048", "seeded-3072", "seeded-4096", "ones-676", "ones-2068", "zeros-1024", "ones_zeros-2048"]
+
+
+def invert_direct_key(ident):
+    """The keys of test_ct_invert_direct_inputs: every words-per-lane form of k_inv_eea_wave with full rows (64 / 128 / 192 / 256
+    words of n^2), a partial two-per-lane row (ones-676: 86 words), five words per lane (ones-2068: 260 words) and structured
+    moduli (zeros at 1024-bit primes, ones_zeros at 2048-bit primes)."""
+    from tests.test_extreme_keys_cpu import load_extreme_keys
+
+    kind, size = ident.rsplit("-", 1)
+    if kind == "seeded":
+        return seeded_key(int(size))
+    if kind == "bench":
+        return bench_key()
+    _, _, b, p, q = next(e for e in load_extreme_keys() if e[0] == ident)
+    return orc.make_key(p, q, djn_x=(1 << 70) + 12345, bits=2 * b)
+
+
+def invert_direct_inputs(key):
+    """Values the extended GCD of pai_ct_invert sees as they are (batches of at most 64 skip the product tree): the neighbours of 0,
+    n, M / 2 and M = n^2, powers of two and their predecessors at the word, lane and top boundaries — a power of two close to M
+    needs about 2 bits(M) halvings, the longest runs below the kernel's step bound —, M minus a power of two, and 27 pattern
+    values (the fixed values are at most 34 distinct ones — 2^1, 2^1 - 1 and M - 2^1 repeat the front, and at one word per lane
+    32 wpl - 1 and 32 wpl repeat 31 and 32 —, so eight pattern values would leave fewer than the 40 required below).  Whatever
+    shares a factor with n is replaced by its neighbour | 1."""
+    import math
+    from tests.test_gpu_extreme_keys import pattern
+
+    n, M = key.n, key.nsq
+    cw = 2 * ((key.bits + 31) // 32)
+    wpl = (cw + 63) // 64
+    mb = M.bit_length()
+    js = [1, 31, 32, 33, 32 * wpl - 1, 32 * wpl, mb - 2, mb - 1]
+    vals = [1, 2, 3, M - 1, M - 2, (M + 1) // 2, n + 1, n - 1, M - n - 1, M - n + 1]
+    vals += [1 << j for j in js] + [(1 << j) - 1 for j in js] + [M - (1 << j) for j in (1, 32, mb - 2)]
+    vals += pattern(M, 27, 99)
+    vals = [v if math.gcd(v, n) == 1 else v | 1 for v in vals]
+    assert all(0 < v < M and math.gcd(v, n) == 1 for v in vals)
+    assert len(set(vals)) >= 40 and len(vals) <= 64, (len(set(vals)), len(vals))
+    return vals
+
+
+@pytest.mark.parametrize("ident", INVERT_DIRECT_KEYS)
+def test_ct_invert_direct_inputs(ident):
+    """pai_ct_invert on batches of at most 64: k_inv_eea_wave on the inputs themselves, not on products — as one call of all values,
+    in place, and as calls of one value — against pow(a, -1, n^2), every row."""
+    nk = NativeKey(invert_direct_key(ident))
+    M = nk.key.nsq
+    a = invert_direct_inputs(nk.key)
+    want = [pow(x, -1, M) for x in a]
+    N = len(a)
+    da = DevArray(ints_to_limbs(a, nk.cw))
+    out = DevArray(shape=(N, nk.cw))
+    _native.check(nk.lib.pai_ct_invert(nk.pk, da.ptr, N, out.ptr, None))
+    got = limbs_to_ints(out.get())
+    assert got == want, (ident, [i for i in range(N) if got[i] != want[i]])
+    assert all(0 < g < M for g in got)
+    for i in range(5):
+        d1 = DevArray(ints_to_limbs(a[i:i + 1], nk.cw))
+        o1 = DevArray(shape=(1, nk.cw))
+        _native.check(nk.lib.pai_ct_invert(nk.pk, d1.ptr, 1, o1.ptr, None))
+        assert limbs_to_ints(o1.get()) == want[i:i + 1], (ident, i)
+    _native.check(nk.lib.pai_ct_invert(nk.pk, da.ptr, N, da.ptr, None))        # in place
+    assert limbs_to_ints(da.get()) == want, ident
+
+
 # ---- round 2: tile I/O kernels, single-product trees, reductions in the library -------------------------------
 @pytest.mark.parametrize("bits", [1024, 2048, 3072, 4096])
 @pytest.mark.parametrize("lat_add", ["0", "4096"])
