@@ -136,11 +136,16 @@ int pai_keygen(int key_bits, int djn, const uint64_t* h_seed, uint32_t* h_p, uin
  * h_base: mod_words words, < modulus; h_out: mod_words words.  Host-only, synchronous. */
 int pai_host_modexp(const uint32_t* h_base, const uint32_t* h_exp, int exp_words, const uint32_t* h_mod, int mod_words,
                     uint32_t* h_out);
+/* h_out = h_a^-1 mod h_m (m_words words, canonical).  PAI_E_INVALID when gcd(a, m) != 1 or m < 2.  a may exceed m.  Any modulus,
+ * even ones included (extended Euclid): the exponents n^-1 mod (s - 1) of pai_recover_r.  Host-only, synchronous. */
+int pai_host_modinv(const uint32_t* h_a, int a_words, const uint32_t* h_m, int m_words, uint32_t* h_out);
 
 /* ipclPrivateKey(pubkey, p, q) — classes.cpp:96-101.  p and q may come in either order; n == p*q is
  * checked.  Derives p^2, q^2, hp, hq, p^-1 mod q. */
 int pai_privkey_create(const pai_pubkey* pk, const uint32_t* h_p, int p_words, const uint32_t* h_q, int q_words,
                        pai_privkey** out);
+/* Every call on sk needs its public handle alive; pai_privkey_destroy alone may come after pai_pubkey_destroy (it frees the private
+ * handle's own device memory on the device recorded at creation and does not look at pk). */
 void pai_privkey_destroy(pai_privkey* sk);
 
 /* ---- hot path --------------------------------------------------------------------------------- */
@@ -165,6 +170,19 @@ int pai_obfuscate(const pai_pubkey* pk, uint32_t* d_ct, const uint32_t* d_r, siz
 
 /* ipclPrivateKey.decrypt(CipherText) — classes.cpp:127-133 (CRT).  d_m: [N][n_words]. */
 int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, void* stream);
+
+/* Ciphertext openings (extension; no reference counterpart).  (m, r) -> (1 + m n) r^n mod n^2 maps Z_n x Z_n^* one-to-one onto the
+ * units modulo n^2, so every ciphertext — fresh, summed, scaled, packed, inverted — has exactly one opening, and the holder of p and
+ * q computes its r by two half-width exponentiations modulo the primes themselves and one Garner lift (k_rrec_a, k_rrec_b).  With m
+ * from pai_decrypt, anyone who holds the public key checks the opening by one standard-scheme encryption with that r, bit for bit.
+ *
+ * d_r[i] = the unique r in [0, n) with r = (d_ct[i] mod s)^(n^-1 mod (s-1)) mod s for s = p, q, Garner-lifted modulo n.
+ * For a unit d_ct[i] this is the r of its opening d_ct[i] = (1 + m n) r^n mod n^2.  d_ct: [N][ct_words] wire form;
+ * d_r: [N][n_words].  A row that shares a factor with n gives the same arithmetic (r_s = 0 for that prime), no error.
+ * The exponents and the constants that reduce a row modulo s are built by the first call; PAI_E_INVALID, and nothing launched, when
+ * n is not coprime to (p - 1)(q - 1) (pai_privkey_create accepts such keys: they decrypt).  One route for every key and batch size;
+ * `PAI_TUNE rrec_grid` caps the workgroups per prime.  Asynchronous on `stream`. */
+int pai_recover_r(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_r, void* stream);
 
 /* Owner-side encryption: pai_encrypt / pai_obfuscate by the party that holds p and q — the same bits for the same r.  Served
  * calls (DJN keys whose primes the encryption digit engine accepts, batches from the hand-over edge `PAI_TUNE crtenc_min` on,

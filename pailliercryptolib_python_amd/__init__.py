@@ -21,13 +21,14 @@ from .paillier import (  # noqa: F401
     BNUtils,
     PaillierEncryptedNumber,
     PaillierKeypair,
+    PaillierOpening,
     PaillierPrivateKey,
     PaillierPublicKey,
 )
 from .packed import PaillierPackedNumber  # noqa: F401
 
 __all__ = [
-    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "PaillierPackedNumber", "BNUtils",
+    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "PaillierPackedNumber", "PaillierOpening", "BNUtils",
     "FixedPointNumber", "context", "hybridControl", "hybridMode",
 ]
 __version__ = "0.1.0"

@@ -54,6 +54,7 @@ PROTOTYPES = {
     "pai_pubkey_destroy": (None, [voidp]),
     "pai_keygen": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint64), voidp, voidp]),
     "pai_host_modexp": (C.c_int, [voidp, voidp, C.c_int, voidp, C.c_int, voidp]),
+    "pai_host_modinv": (C.c_int, [voidp, C.c_int, voidp, C.c_int, voidp]),
     "pai_pubkey_info": (C.c_int, [voidp] + [C.POINTER(C.c_int)] * 7),
     "pai_pubkey_table_info": (C.c_int, [voidp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pai_path_edges": (C.c_int, [voidp, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int)]),
@@ -64,6 +65,7 @@ PROTOTYPES = {
     "pai_encrypt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_obfuscate": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
     "pai_decrypt": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
+    "pai_recover_r": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_encrypt_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_obfuscate_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
     "pai_privkey_crt_table_info": (C.c_int, [voidp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -180,6 +182,21 @@ def host_modexp(base: int, exp: int, mod: int) -> int:
     m = np.frombuffer(mod.to_bytes(4 * mw, "little"), dtype=np.uint32).copy()
     out = np.zeros(mw, dtype=np.uint32)
     check(load().pai_host_modexp(b.ctypes.data, e.ctypes.data, ew, m.ctypes.data, mw, out.ctypes.data))
+    return int.from_bytes(out.tobytes(), "little")
+
+
+def host_modinv(a: int, mod: int) -> int:
+    """pai_host_modinv: a^-1 mod any modulus >= 2, even ones included (NativeError PAI_E_INVALID when gcd(a, mod) != 1)."""
+    import numpy as np
+
+    if a < 0 or mod < 0:
+        raise ValueError("host_modinv: operands must be non-negative")
+    aw = max(1, (a.bit_length() + 31) // 32)
+    mw = max(1, (mod.bit_length() + 31) // 32)
+    av = np.frombuffer(a.to_bytes(4 * aw, "little"), dtype=np.uint32).copy()
+    mv = np.frombuffer(mod.to_bytes(4 * mw, "little"), dtype=np.uint32).copy()
+    out = np.zeros(mw, dtype=np.uint32)
+    check(load().pai_host_modinv(av.ctypes.data, aw, mv.ctypes.data, mw, out.ctypes.data))
     return int.from_bytes(out.tobytes(), "little")
 
 

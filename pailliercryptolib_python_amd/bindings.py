@@ -279,6 +279,16 @@ class ipclPublicKey:
         this key (pai_pubkey_trim) — they are rebuilt / re-grown on demand.  Returns the device bytes released."""
         return sum(h.trim() for h in self._handles.values())
 
+    def standard_twin(self) -> "ipclPublicKey":
+        """Extension: the standard-scheme key of the same n on the home device, built once (openings are checked by a
+        standard-scheme encryption with an explicit r: paillier.PaillierPublicKey.verify_opening).  A standard key is its own."""
+        if not self._djn:
+            return self
+        tw = self.__dict__.get("_std_twin")
+        if tw is None or tw._device_list()[0] != self.handle.device:
+            tw = self.__dict__["_std_twin"] = ipclPublicKey(self._n, self._bits, False, device=self.handle.device)
+        return tw
+
     def fanout_devices(self, n_items: int) -> Optional[List[torch.device]]:
         """The device list to shard a batch of n_items over, or None when it should stay on the home device."""
         devs = self._device_list()
@@ -490,6 +500,20 @@ class ipclPrivateKey:
             return hg.decrypt(ct_sh[g]) if count else hg.pub.empty_pt(0)
 
         return engine.gather_shards(engine.fan_out(devs, work, words.shape[0]), hpub.device)
+
+    # -- ciphertext openings (extension): the r of ct = (1 + m n) r^n mod n^2, which only the holder of p and q can compute --------
+    def recover_r_words(self, ct: torch.Tensor) -> torch.Tensor:
+        """Ciphertexts [N, ct_words] -> the randomness of their openings [N, n_words] (pai_recover_r).  Runs on the home device;
+        keys on a device list recover there too."""
+        hpub = self.handle.pub
+        words = ct if ct.device == hpub.device else ct.to(hpub.device)
+        return self.handle.recover_r(words.contiguous())
+
+    def recover_r(self, ct: "ipclCipherText") -> "ipclPlainText":
+        if ct.public_key._n != self._pk._n:
+            raise RuntimeError("ipclPrivateKey.recover_r: public key mismatch")
+        ct._check()                                          # as decrypt: a failed asynchronous inversion is raised on its own result
+        return ipclPlainText(self.recover_r_words(ct._t))
 
     # -- owner-side encryption (extension): the holder of p and q computes hs^r modulo p^2 and q^2 and lifts ------------------
     def _single_device(self, count: int) -> bool:

@@ -10,6 +10,7 @@ int pai_privkey_create(const pai_pubkey* pk, const uint32_t* h_p, int p_words, c
         std::unique_ptr<pai_privkey, PrivkeyDeleter> sk(new pai_privkey());
         DeviceScope scope_(pk->device);
         sk->pk = pk;
+        sk->device = pk->device;
         Limbs p = hbn::from_u32(h_p, (size_t)p_words), q = hbn::from_u32(h_q, (size_t)q_words);
         if (hbn::cmp(p, q) > 0) std::swap(p, q);            // upstream keeps p < q
         require(hbn::cmp(p, q) != 0, "p and q must differ");
@@ -102,7 +103,9 @@ void pai_privkey_destroy(pai_privkey* sk) {
     if (!sk) return;
     int prev_ = -1;
     (void)hipGetDevice(&prev_);
-    (void)hipSetDevice(sk->pk ? sk->pk->device : 0);
+    // (the handle's own copy of the device: garbage collectors destroy the two handles of a key in either order, and a device read
+    // from a freed public handle made hipSetDevice fail with "invalid device ordinal", an error the caller's NEXT HIP call reported)
+    (void)hipSetDevice(sk->device);
     for (int w = 0; w < 2; ++w) {
         sk->sq[w].release();
         sk->pr[w].release();
@@ -146,6 +149,7 @@ void pai_privkey_destroy(pai_privkey* sk) {
     if (sk->lat.d_pinvqR) (void)hipFree(sk->lat.d_pinvqR);
     sk->lat.table.release();
     release_crt(sk);
+    release_rec(sk);
     sk->table.release();
     sk->wscratch.release();
     sk->ubuf.release();

@@ -149,6 +149,12 @@ struct GeoInst {
             launch(k_modmul_msb<GM>, dim3(grid), dim3(BLOCK_THREADS), MsbLds<GM>::WORDS * 4, s, c, a, b, out, n, w32);
         }
     }
+    static void rrec_a(hipStream_t s, int gridx, RrecAParams P, const uint32_t* ct, uint32_t* r_out, int n, uint32_t* table) {
+        launch(k_rrec_a<G, MODEXP_WINDOW>, dim3(gridx, 2), dim3(BLOCK_THREADS), G::LDS_BYTES, s, P, ct, r_out, n, table);
+    }
+    static void rrec_b(hipStream_t s, int grid, RrecBParams P, const uint32_t* r_in, uint32_t* r_out, int n) {
+        launch(k_rrec_b<G>, dim3(grid), dim3(BLOCK_THREADS), 2 * G::LDS_WORDS * 4, s, P, r_in, r_out, n);
+    }
     static size_t table_words(size_t blocks) { return (size_t)(1u << MODEXP_WINDOW) * G::NL * blocks * G::EPB; }
 
     static const GeoOps* ops() {
@@ -177,6 +183,8 @@ struct GeoInst {
             t.segprod = &segprod;
             t.segscan = &segscan;
             t.smexp = &smexp;
+            t.rrec_a = &rrec_a;
+            t.rrec_b = &rrec_b;
             return t;
         }();
         return &o;

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "kernels_paillier.hpp"
+#include "kernels_recover.hpp"
 #include "mont_msb.hpp"
 
 namespace pai {
@@ -62,6 +63,10 @@ struct GeoOps {
     // sparse multi-exponentiation (k_smexp): chunks of a term list over the tables of mexp_table, one partial per chunk
     void (*smexp)(hipStream_t, int grid, const MontCtx*, MexpParams, SmexpArgs, const uint32_t* table, const uint32_t* e,
                   const uint8_t* sign, uint32_t* out, int nlanes);
+    // randomness recovery (kernels_recover.hpp) on the geometry of the primes: stage A (grid = gridx x 2 primes, table scratch of
+    // table_words(2 gridx) words), stage B
+    void (*rrec_a)(hipStream_t, int gridx, RrecAParams, const uint32_t* ct, uint32_t* r_out, int n, uint32_t* table);
+    void (*rrec_b)(hipStream_t, int grid, RrecBParams, const uint32_t* r_in, uint32_t* r_out, int n);
 };
 
 const GeoOps* geo_ops_36x1();

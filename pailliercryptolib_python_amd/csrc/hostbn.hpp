@@ -197,6 +197,28 @@ inline Limbs inv_mod_prime(const Limbs& a, const Limbs& p) {
     return mt.powmod(a, sub(p, Limbs{2u}));
 }
 
+// a^-1 mod m for ANY modulus m >= 2, even ones included (the recovery exponents n^-1 mod (s - 1)): extended Euclid on divq.
+// The cofactors t_k of a alternate in sign, so t_(k+1) = t_(k-1) - q t_k is an addition of magnitudes and one sign bit.
+// Returns false — *out untouched — when gcd(a, m) != 1 or m < 2; a may exceed m.
+inline bool inv_mod(const Limbs& a, const Limbs& m, Limbs* out) {
+    if (cmp(m, Limbs{2u}) < 0) return false;
+    Limbs r0 = m, r1 = mod(a, m), t0, t1{1u};
+    bool neg0 = false, neg1 = false;                  // signs of t0, t1 (t0 = 0 at the start)
+    while (!is_zero(r1)) {
+        Limbs rem;
+        const Limbs q = divq(r0, r1, &rem);
+        Limbs t2 = add(t0, mul(q, t1));
+        const bool neg2 = !neg1;
+        r0 = r1; r1 = rem;
+        t0 = t1; neg0 = neg1;
+        t1 = t2; neg1 = neg2;
+    }
+    if (cmp(r0, Limbs{1u}) != 0) return false;
+    const Limbs t = mod(t0, m);
+    *out = (neg0 && !is_zero(t)) ? sub(m, t) : t;
+    return true;
+}
+
 // a^-1 mod 2^bits for odd a (Hensel/Newton lifting on truncated products)
 inline Limbs inv_mod_pow2(const Limbs& a, int bits) {
     if (!is_odd(a)) throw std::runtime_error("inv_mod_pow2: even input");

@@ -389,7 +389,8 @@ struct ScopedKernelTimer {
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
 //                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels),
-//                                  quantize_blocks (workgroups pai_fp_quantize aims at; default 4 per CU)
+//                                  quantize_blocks (workgroups pai_fp_quantize aims at; default 4 per CU),
+//                                  rrec_grid (most workgroups per prime of k_rrec_a: a small batch then walks the tile loop)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -600,6 +601,7 @@ struct pai_pubkey {
 
 struct pai_privkey {
     const pai_pubkey* pk = nullptr;
+    int device = 0;               // pk->device, kept here: pai_privkey_destroy must not look at a public handle that may be gone already
     Limbs p, q;
     ModSetup sq[2];               // p^2, q^2
     ModSetup pr[2];               // p, q
@@ -685,6 +687,16 @@ struct pai_privkey {
         int pp_nd = 0, pp_nch = 0;
         int pp_chain = 1;                 // limbs per lane of the chain's contexts (both primes)
     } lat;
+    // Randomness recovery (dispatch_recover.hpp): the exponents d_s = n^-1 mod (s - 1), the constants R^(i+2) mod s that take a
+    // ciphertext row into Montgomery form modulo s, and the scratch of k_rrec_a / k_rrec_b; built by the first pai_recover_r
+    struct Rec {
+        bool tried = false, ok = false;
+        uint32_t* d_expo[2] = {nullptr, nullptr};
+        int ewords[2] = {0, 0}, ebits[2] = {0, 0};
+        uint32_t* d_kdig[2] = {nullptr, nullptr};    // [nd][NL]
+        int nd = 0, r_words = 0;
+        DevBuf table, rs;                 // window tables of stage A, the residues [2][N][r_words]
+    } rec;
     ScratchOrder order;
     std::mutex mu;
 };
@@ -733,6 +745,18 @@ int pai_host_modexp(const uint32_t* h_base, const uint32_t* h_exp, int exp_words
         require(kg::cmp(b, mt.m, Lt) < 0, "pai_host_modexp: base must be reduced modulo the modulus");
         mt.pow(out, b, e.data(), eL);
         std::memcpy(h_out, out, 4 * (size_t)mod_words);
+    });
+}
+
+int pai_host_modinv(const uint32_t* h_a, int a_words, const uint32_t* h_m, int m_words, uint32_t* h_out) {
+    return guarded([&] {
+        require(h_a && h_m && h_out, "pai_host_modinv: NULL pointer");
+        require(a_words >= 1 && m_words >= 1, "pai_host_modinv: bad word count");
+        const Limbs a = hbn::from_u32(h_a, (size_t)a_words), m = hbn::from_u32(h_m, (size_t)m_words);
+        require(hbn::cmp(m, Limbs{2u}) >= 0, "pai_host_modinv: the modulus must be at least 2");
+        Limbs inv;
+        require(hbn::inv_mod(a, m, &inv), "pai_host_modinv: no inverse (gcd(a, m) != 1)");
+        for (int i = 0; i < m_words; ++i) h_out[i] = (size_t)i < inv.size() ? inv[(size_t)i] : 0u;
     });
 }
 
@@ -1375,6 +1399,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_scan.hpp"
 #include "dispatch_pack.hpp"
 #include "dispatch_encrypt_crt.hpp"
+#include "dispatch_recover.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

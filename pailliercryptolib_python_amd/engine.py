@@ -693,6 +693,13 @@ class PrivateKeyHandle:
         _native.check(self.lib.pai_decrypt(self.h, _ptr(ct), ct.shape[0], _ptr(out), _stream(self.pub.device)))
         return out
 
+    def recover_r(self, ct: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pai_recover_r: the r of every row's opening ct = (1 + m n) r^n mod n^2, [N, n_words]."""
+        self.pub._chk(ct, self.pub.ct_words, "ct")
+        out = self.pub.empty_pt(ct.shape[0]) if out is None else out
+        _native.check(self.lib.pai_recover_r(self.h, _ptr(ct), ct.shape[0], _ptr(out), _stream(self.pub.device)))
+        return out
+
     # -- owner-side encryption (pai_encrypt_crt / pai_obfuscate_crt): the bits of PublicKeyHandle.encrypt / obfuscate_ ----------
     def encrypt(self, m: torch.Tensor, r: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         pub = self.pub

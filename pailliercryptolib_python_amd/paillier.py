@@ -112,6 +112,61 @@ class PaillierPublicKey:
         return _packed.encrypt_packed(self, values, exponent=exponent, value_bits=value_bits, slot_bits=slot_bits, slots=slots,
                                       apply_obfuscator=apply_obfuscator, r=r, _encrypt_words=_encrypt_words)
 
+    def verify_opening(self, x, opening) -> np.ndarray:
+        """Extension: checks openings of the ciphertexts of `x` (a PaillierEncryptedNumber or PaillierPackedNumber) with the public
+        key alone: element i is True iff (1 + m_i n) r_i^n mod n^2 is ciphertext i, bit for bit — one standard-scheme encryption
+        per element on the device.  `opening` is a PaillierOpening (its exponents are compared too) or a pair (m_ints, r_ints).
+        m_i >= n, r_i = 0 and r_i >= n make element i False, never an exception; a length mismatch is a ValueError."""
+        pub = self.pubkey
+        ct = x.ciphertext()
+        if ct.public_key._n != self.n:
+            raise ValueError("PaillierPublicKey.verify_opening: public key mismatch")
+        words = ct.words
+        rows = int(words.shape[0])
+        h = pub.handle
+        ok = np.ones(rows, dtype=bool)
+        if isinstance(opening, PaillierOpening):
+            if opening.public_key.n != self.n:
+                raise ValueError("PaillierPublicKey.verify_opening: the opening belongs to another key")
+            if len(opening) != rows:
+                raise ValueError(f"PaillierPublicKey.verify_opening: {rows} ciphertexts, {len(opening)} openings")
+            m_t, r_t = opening._words(h.device)
+            expo = getattr(x, "_expo", None)
+            if expo is not None and opening._expo is not None:
+                ok &= np.asarray(expo, dtype=np.int64) == np.asarray(opening._expo, dtype=np.int64)
+        else:
+            try:
+                m_in, r_in = opening
+            except (TypeError, ValueError):
+                raise TypeError("PaillierPublicKey.verify_opening: expected a PaillierOpening or a pair (m, r)") from None
+            ms = [int(m_in)] if isinstance(m_in, (int, np.integer)) else [int(v) for v in m_in]
+            rs = [int(r_in)] if isinstance(r_in, (int, np.integer)) else [int(v) for v in r_in]
+            if len(ms) != rows or len(rs) != rows:
+                raise ValueError(f"PaillierPublicKey.verify_opening: {rows} ciphertexts, {len(ms)} values of m, {len(rs)} of r")
+            if rows == 0:
+                return ok
+            # values that do not fit a row of words are False already; the row that stands in for them is checked like any other
+            fit = np.array([0 <= m < self.n and 0 < r < self.n for m, r in zip(ms, rs)], dtype=bool).reshape(rows)
+            ok &= fit
+            m_t = engine.to_device_words(engine.ints_to_words([m if f else 0 for m, f in zip(ms, fit)], h.n_words), h.device)
+            r_t = engine.to_device_words(engine.ints_to_words([r if f else 1 for r, f in zip(rs, fit)], h.n_words), h.device)
+        if rows == 0:
+            return ok
+        # range checks on the device: the kernels take residues, and (m + n, r) or (m, r + n) must not pass for (m, r)
+        n_w = torch.from_numpy(engine.int_to_words(self.n, h.n_words).astype(np.int64)).to(h.device)
+        bad_r = _bindings._rows_not_in_1_n(r_t, n_w)
+        bad_m = _bindings._rows_not_in_1_n(m_t, n_w) & ((m_t != 0).any(dim=1))
+        bad = bad_r | bad_m
+        if bool(bad.any()):
+            keep = (~bad).to(m_t.dtype).unsqueeze(1)
+            one = torch.zeros_like(r_t[:1])
+            one[0, 0] = 1
+            m_t = m_t * keep
+            r_t = r_t * keep + one * (1 - keep)
+        again = pub.standard_twin().encrypt_words(m_t.contiguous(), True, r_t.contiguous())
+        same = (again == words).all(dim=1) & ~bad
+        return ok & same.cpu().numpy()
+
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
         exponents (pai_fp_encode_at: the plaintext side of ct + plaintext, see encrypt's _align_to), or None when the batch
@@ -372,6 +427,35 @@ class PaillierPrivateKey:
         m, wide = self._decrypt_packed(p)
         return _packed.mantissas_to_ints(m, wide)
 
+    # -- ciphertext openings (extension): every ciphertext is (1 + m n) r^n mod n^2 for exactly one (m, r) -----------------------
+    def _recover_words(self, x, what: str) -> torch.Tensor:
+        from . import packed as _packed
+
+        if not isinstance(x, (PaillierEncryptedNumber, _packed.PaillierPackedNumber)):
+            raise TypeError(f"PaillierPrivateKey.{what}: expected a PaillierEncryptedNumber or a PaillierPackedNumber")
+        if x.public_key.n != self.__n:
+            raise ValueError(f"PaillierPrivateKey.{what}: Public key mismatch")
+        return self.prikey.recover_r_words(x.ciphertext().words)
+
+    def recover_randomness(self, x):
+        """Extension: the r of every ciphertext of `x` (a PaillierEncryptedNumber or a PaillierPackedNumber: one per row) as
+        Python ints — a single int when there is one —, computed with p and q (pai_recover_r).  With the residue m of
+        raw_decrypt, (m, r) is the ciphertext's opening: PaillierPublicKey.verify_opening checks it with the public key alone.
+        Holds for sums, scalar products, packed rows and inverses as for fresh encryptions."""
+        ret = engine.words_to_ints(engine.to_host_words(self._recover_words(x, "recover_randomness")))
+        return ret if len(ret) != 1 else ret[0]
+
+    def open(self, enc: "PaillierEncryptedNumber") -> "PaillierOpening":
+        """Extension: the openings (m_i, r_i) of a PaillierEncryptedNumber — residues from the usual decryption, randomness from
+        pai_recover_r, both left on the device — with the container's exponents and length."""
+        if not isinstance(enc, PaillierEncryptedNumber):
+            raise TypeError("PaillierPrivateKey.open: expected a PaillierEncryptedNumber")
+        if enc.public_key.n != self.__n:
+            raise ValueError("PaillierPrivateKey.open: Public key mismatch")
+        m = self.prikey.decrypt_words(enc.words)
+        r = self._recover_words(enc, "open")
+        return PaillierOpening(enc.public_key, m, r, enc._expo, len(enc))
+
     def decrypt_to_numpy(self, encrypted_number: "PaillierEncryptedNumber") -> np.ndarray:
         """Extension: the decoded values as a float64 ndarray without per-element Python objects."""
         if encrypted_number.public_key.n != self.__n:
@@ -380,6 +464,72 @@ class PaillierPrivateKey:
         if mant is not None:
             return np.ldexp(mant.astype(np.float64), -np.asarray(encrypted_number._expo, dtype=np.int64).astype(np.int32))
         return _fp.decode_float64_array(words, encrypted_number._expo, self.__n, self.__max_int)
+
+
+class PaillierOpening:
+    """The openings (m_i, r_i) of the ciphertexts of one container: ciphertext i is (1 + m_i n) r_i^n mod n^2
+    (PaillierPrivateKey.open).  Residues and randomness rest on the key's device as limb matrices; the exponents and the length
+    are the container's.  PaillierPublicKey.verify_opening checks an opening without the private key."""
+
+    def __init__(self, public_key: PaillierPublicKey, m, r, exponents, length: int):
+        if m.shape != r.shape:
+            raise ValueError("PaillierOpening: m and r must have the same shape")
+        self.public_key = public_key
+        self._m, self._r = m, r                          # [N, n_words]: device tensors, or host words after unpickling
+        self._expo = None if exponents is None else np.asarray(exponents, dtype=np.int32).reshape(-1).copy()
+        self.__length = int(length)
+
+    def __len__(self) -> int:
+        return self.__length
+
+    def __repr__(self):
+        return f"<PaillierOpening of {self.__length} ciphertexts>"
+
+    def _words(self, device):
+        """(m, r) as limb matrices on `device`."""
+        if isinstance(self._m, np.ndarray):
+            self._m, self._r = engine.to_device_words(self._m, device), engine.to_device_words(self._r, device)
+        if self._m.device != device:
+            return self._m.to(device), self._r.to(device)
+        return self._m, self._r
+
+    def _host(self, t) -> np.ndarray:
+        return t if isinstance(t, np.ndarray) else engine.to_host_words(t)
+
+    def raw(self):
+        """The residues m_i as Python ints (a single int when the length is 1), as PaillierPrivateKey.raw_decrypt."""
+        ret = engine.words_to_ints(self._host(self._m))
+        return ret if self.__length > 1 else ret[0]
+
+    def randomness(self):
+        """The r_i as Python ints (a single int when the length is 1)."""
+        ret = engine.words_to_ints(self._host(self._r))
+        return ret if self.__length > 1 else ret[0]
+
+    def exponent(self):
+        return None if self._expo is None else [int(e) for e in self._expo]
+
+    def decode(self):
+        """What PaillierPrivateKey.decrypt returns for the container this opening was taken from."""
+        pk = self.public_key
+        words = None
+        if pk.n.bit_length() > 66:
+            h = pk.pubkey.handle
+            mant, flag = h.fp_decode_i64(self._words(h.device)[0])
+            if not bool(flag.any()):
+                ret = _fp.decode_mantissas(mant.cpu().numpy(), self._expo)
+                return ret if self.__length > 1 else ret[0]
+        words = self._host(self._m)
+        ret = _fp.decode_array(words, self._expo, pk.n, pk.max_int)
+        return ret if self.__length > 1 else ret[0]
+
+    def __getstate__(self) -> tuple:
+        return (self.public_key, self.__length, None if self._expo is None else [int(e) for e in self._expo],
+                np.ascontiguousarray(self._host(self._m)), np.ascontiguousarray(self._host(self._r)))
+
+    def __setstate__(self, state: tuple):
+        (self.public_key, self.__length, expo, self._m, self._r) = state
+        self._expo = None if expo is None else np.asarray(expo, dtype=np.int32).reshape(-1).copy()
 
 
 # batches from this size on are sorted by |exponent difference| before a fused aligned addition (PAI_ALIGN_SORT_MIN)
