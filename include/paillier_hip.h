@@ -184,6 +184,26 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
  * `PAI_TUNE rrec_grid` caps the workgroups per prime.  Asynchronous on `stream`. */
 int pai_recover_r(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_r, void* stream);
 
+/* Batch verification of openings (extension): the two sides of the small-exponent test, one exponentiation by n per SEGMENT instead
+ * of one per row.  The N rows are cut into S = ceil(N / seg_len) segments of consecutive rows (the last may be short); with the
+ * caller's coefficients e_i,
+ *     d_lhs[s] = prod ct_i^(e_i) mod n^2,      d_rhs[s] = (1 + n M_s) B_s^n mod n^2,
+ *     M_s = sum e_i m_i mod n,                 B_s = prod r_i^(e_i) mod n          (over the rows i of segment s),
+ * both [S][ct_words] canonical residues in the wire form.  If every ct_i = (1 + m_i n) r_i^n mod n^2 the two agree for any
+ * coefficients; comparing them, and what an agreement proves for secret random coefficients, is the caller's business
+ * (PaillierPublicKey.verify_openings).  *d_flag is one device word the caller zeroes: bit 0 is set when some B_s is not a unit modulo n —
+ * the rows of d_rhs then prove nothing (a multiple of a prime factor squares to 0 in that component on both sides).
+ * d_ct: [N][ct_words] residues modulo n^2; d_m, d_r: [N][n_words] residues modulo n (range checks are the caller's: a row the caller
+ * excludes enters as ct = 1, m = 0, r = 1); d_e: [N][e_words] little-endian words of at most ebits_max
+ * bits, 1 <= e_words <= 8, 0 < ebits_max <= 32 e_words; seg_len >= 1 — anything else is PAI_E_INVALID and launches nothing.
+ * Keys the digit engine serves fold r and m modulo n in k_open_fold over the chunk plan of the ciphertexts' sparse
+ * multi-exponentiation; wider keys, and every key under PAI_DISABLE=open_fold, run three sparse multi-exponentiations modulo n^2
+ * instead — the same bits.  PAI_TUNE open_chunk: elements per lane (default: smexp_chunk's rule); open_wbits: window of the chain
+ * modulo n.  A call whose power tables do not fit the device is cut into row blocks on segment boundaries.  Synchronises `stream`
+ * (the combine steps' sizes). */
+int pai_opening_fold(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_m, const uint32_t* d_r, size_t N, const uint32_t* d_e,
+                     int e_words, int ebits_max, size_t seg_len, uint32_t* d_lhs, uint32_t* d_rhs, int32_t* d_flag, void* stream);
+
 /* Owner-side encryption: pai_encrypt / pai_obfuscate by the party that holds p and q — the same bits for the same r.  Served
  * calls (DJN keys whose primes the encryption digit engine accepts, batches from the hand-over edge `PAI_TUNE crtenc_min` on,
  * PAI_DISABLE=crtenc not set) compute hs^r as two half-width fixed-base exponentiations modulo p^2 and q^2 and one Garner lift

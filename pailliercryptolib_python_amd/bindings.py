@@ -289,6 +289,13 @@ class ipclPublicKey:
             tw = self.__dict__["_std_twin"] = ipclPublicKey(self._n, self._bits, False, device=self.handle.device)
         return tw
 
+    def opening_fold_words(self, ct: torch.Tensor, m: torch.Tensor, r: torch.Tensor, e: torch.Tensor, ebits: int, seg_len: int):
+        """Extension: (lhs, rhs, flag) of the batch test of openings per segment (engine.PublicKeyHandle.opening_fold), on the home
+        device; operands on another device are brought there."""
+        h = self.handle
+        ct, m, r, e = (t if t.device == h.device else t.to(h.device) for t in (ct, m, r, e))
+        return h.opening_fold(ct.contiguous(), m.contiguous(), r.contiguous(), e.contiguous(), ebits, seg_len)
+
     def fanout_devices(self, n_items: int) -> Optional[List[torch.device]]:
         """The device list to shard a batch of n_items over, or None when it should stay on the home device."""
         devs = self._device_list()

@@ -40,6 +40,7 @@ SOURCES = [
     "padic_enc36_kernels.hip",
     "pair_kernels.hip",
     "crt_lift_kernels.hip",
+    "open_fold_kernels.hip",
     "paillier_capi.hip",
 ]
 

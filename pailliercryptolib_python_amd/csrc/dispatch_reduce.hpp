@@ -170,6 +170,128 @@ int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, in
 //   2. terms: the segment offsets made safe (k_smexp_offsets), cut into chunks of <= C terms (k_seg_chunk_scan / _expand), one
 //      Straus chain per chunk into a partial (k_smexp_padic / k_smexp);
 //   3. combine: the partials of a segment multiplied by the levels of pai_ct_segment_prod at shift 0 (an empty segment gives 1).
+// The chunk plan a sparse product ran on (valid until the handle's next sparse product): pai_opening_fold folds r and m over the same chunks
+struct SmexpPlan {
+    const int64_t* cstart = nullptr;   // [S + 1] chunks before every segment
+    const int64_t* coff = nullptr;     // [nlanes + 1] first term of every chunk
+    size_t nlanes = 0, chunk = 0;
+};
+// The three stages, under pk->mu on the key's device; S > 0.  chunk_force != 0 sets the terms per lane (pai_opening_fold's open_chunk).
+static void sparse_multiexp_locked(const pai_pubkey* pk, hipStream_t s, const uint32_t* d_ct, const uint32_t* d_ct_inv, size_t N,
+                                   const int32_t* d_base, const uint32_t* d_e, int e_words, int ebits_max, const uint8_t* d_sign, size_t T,
+                                   const int64_t* d_offsets, size_t S, uint32_t* d_out, size_t chunk_force = 0, SmexpPlan* plan = nullptr) {
+    const GeoOps* lg = pk->msq.geo;                   // lane-group engine when the digit engine does not serve the key
+    const bool digit = pk->penc_nl != 0;
+    const int nsigns = d_sign ? 2 : 1;
+    const int pnl = digit ? pk->penc_nl : (lg->nl + 1) / 2;
+    const int lanes_per_wg = digit ? BLOCK_THREADS : lg->epb;
+    size_t want_lanes = (size_t)pk->dev.ncu * lanes_per_wg * (digit ? 2 : 4);
+    if (long long v; knob_tune("mexp_lanes", &v) && v > 0) want_lanes = (size_t)v;
+    const size_t C = chunk_force ? chunk_force : smexp_chunk(want_lanes, T);      // path_ranges.hpp
+    // chunks: at most ceil(len / C) per segment, i.e. <= T / C + (nonempty segments); the tail of them empty
+    const size_t nlanes = T == 0 ? 0 : std::min(T, T / C + std::min(S, T));
+    size_t mem_free = 0, mem_total = 0;
+    HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+    // window width: as pai_ct_multiexp, with the table cost of a base amortised over its T / N terms
+    int wbits = 2;
+    {
+        double best = 1e300;
+        const double uses = N ? std::max(1.0, (double)T / (double)N) : 1.0;
+        for (int w = 2; w <= 7; ++w) {
+            const double tb = (double)N * nsigns * (double)((size_t)1 << w) * 2.0 * pnl * 4.0;
+            if (w > 2 && tb > (double)mem_total / 16.0) break;
+            const double cost = (double)((ebits_max + w - 1) / w) + (double)nsigns * (double)(((size_t)1 << w) - 2) / uses;
+            if (cost < best) { best = cost; wbits = w; }
+        }
+        if (long long v; knob_tune("mexp_wbits", &v) && v >= 1 && v <= 8) wbits = (int)v;
+    }
+    const size_t table_bytes = N * nsigns * ((size_t)1 << wbits) * 2 * (size_t)pnl * 4;
+    const size_t part_bytes = nlanes * (size_t)pk->ct_words * 4;
+    if (T && (table_bytes > mem_total / 8 ||
+              table_bytes + part_bytes > mem_free + pk->mexp_table.bytes + pk->mexp_partial.bytes))
+        throw PaiError(PAI_E_UNSUPPORTED, "power tables of this sparse product do not fit the device");
+    // plan scratch: clean offsets [S + 1], chunk starts per segment [S + 1], first term per chunk [nlanes + 1]
+    pk->smexp_plan.ensure((2 * (S + 1) + nlanes + 1) * sizeof(int64_t));
+    int64_t* clean = pk->smexp_plan.as<int64_t>();
+    int64_t* cstart = clean + (S + 1);
+    int64_t* coff = cstart + (S + 1);
+    int* status = status_word(pk, s);
+    {
+        OrderScope order_(pk->order, s);
+        hipLaunchKernelGGL(k_smexp_offsets, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, d_offsets, (int)S, (int64_t)T, clean, status);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_seg_chunk_scan, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, clean, (int)S, (int64_t)C, cstart);
+        HIP_CHECK(hipGetLastError());
+        if (nlanes) {
+            pk->mexp_table.ensure(table_bytes);
+            pk->mexp_partial.ensure(part_bytes);
+            const int eg = (int)std::min<size_t>((nlanes + 1 + 255) / 256, 1024);
+            hipLaunchKernelGGL(k_seg_chunk_expand, dim3(eg), dim3(256), 0, s, clean, cstart, (int)S, (int64_t)C, coff, nlanes);
+            HIP_CHECK(hipGetLastError());
+            SmexpArgs A;
+            A.base = d_base; A.coff = coff; A.status = status; A.nbases = (int)N;
+            if (digit) {
+                MexpPadicParams Q;
+                Q.nctx = pk->nmod.d_ctx;
+                Q.nm1 = pk->d_nm1;
+                Q.nsq = pk->d_nsq29;
+                Q.kdig = pk->d_ct_kdig;
+                Q.one_dig = pk->d_one_dig;
+                Q.mscratch = reinterpret_cast<uint4*>(pk->d_mscratch);
+                Q.table = pk->mexp_table.as<uint4>();
+                Q.nd = pk->ct_nd;
+                Q.ct_words = pk->ct_words;
+                Q.R = 1; Q.K = (int)N; Q.M = 1; Q.chunk = (int)C; Q.nsigns = nsigns;
+                Q.e_words = e_words;
+                Q.ebits_max = ebits_max;
+                Q.by_rows = 0;
+                Q.wbits = wbits;
+                if (N) {
+                    const size_t tl = N * nsigns, tiles = (tl + BLOCK_THREADS - 1) / BLOCK_THREADS;
+                    const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
+                    ScopedKernelTimer t("k_mexp_table", s);
+                    launcher(padic_enc_ops(pnl), &PadicEncOps::mexp_table, "no multi-exponentiation kernel for this limb count")(
+                        s, grid, Q, d_ct, d_ct_inv, (int)tl);
+                    t.stop();
+                    HIP_CHECK(hipGetLastError());
+                }
+                {
+                    const size_t tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
+                    const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
+                    ScopedKernelTimer t("k_smexp", s);
+                    launcher(padic_enc_ops(pnl), &PadicEncOps::smexp, "no multi-exponentiation kernel for this limb count")(
+                        s, grid, Q, A, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes);
+                    t.stop();
+                    HIP_CHECK(hipGetLastError());
+                }
+            } else {
+                MexpParams P;
+                P.R = 1; P.K = (int)N; P.M = 1; P.chunk = (int)C; P.nsigns = nsigns;
+                P.e_words = e_words; P.ebits_max = ebits_max; P.wbits = wbits; P.w32 = pk->ct_words;
+                if (N) {
+                    const size_t tl = N * nsigns;
+                    ScopedKernelTimer t("k_mexp_table", s);
+                    lg->mexp_table(s, grid_for(lg, tl, pk->dev.ncu), pk->msq.d_ctx, d_ct, d_ct_inv, pk->ct_words, pk->mexp_table.as<uint32_t>(),
+                                   (int)tl, nsigns, wbits);
+                    t.stop();
+                    HIP_CHECK(hipGetLastError());
+                }
+                {
+                    ScopedKernelTimer t("k_smexp", s);
+                    lg->smexp(s, grid_for(lg, nlanes, pk->dev.ncu), pk->msq.d_ctx, P, A, pk->mexp_table.as<uint32_t>(), d_e, d_sign,
+                              pk->mexp_partial.as<uint32_t>(), (int)nlanes);
+                    t.stop();
+                    HIP_CHECK(hipGetLastError());
+                }
+            }
+        }
+        order_.done();
+    }
+    // the partials of segment s are rows cstart[s] .. cstart[s + 1] - 1, in the wire form (tag 0), all at shift 0
+    segment_prod_locked(pk, s, nlanes ? pk->mexp_partial.as<uint32_t>() : nullptr, nlanes, 0, nullptr, nullptr, cstart, S, d_out);
+    if (plan) { plan->cstart = cstart; plan->coff = coff; plan->nlanes = nlanes; plan->chunk = C; }
+}
+
 int pai_ct_sparse_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_ct_inv, size_t N, const int32_t* d_base,
                            const uint32_t* d_e, int e_words, int ebits_max, const uint8_t* d_sign, size_t T, const int64_t* d_offsets,
                            size_t S, uint32_t* d_out, void* stream) {
@@ -184,117 +306,8 @@ int pai_ct_sparse_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uin
         if (S == 0) return;
         std::lock_guard<std::mutex> lk(pk->mu);
         DeviceScope scope_(pk->device);
-        hipStream_t s = (hipStream_t)stream;
         g_last_times.clear();
-        const GeoOps* lg = pk->msq.geo;                   // lane-group engine when the digit engine does not serve the key
-        const bool digit = pk->penc_nl != 0;
-        const int nsigns = d_sign ? 2 : 1;
-        const int pnl = digit ? pk->penc_nl : (lg->nl + 1) / 2;
-        const int lanes_per_wg = digit ? BLOCK_THREADS : lg->epb;
-        size_t want_lanes = (size_t)pk->dev.ncu * lanes_per_wg * (digit ? 2 : 4);
-        if (long long v; knob_tune("mexp_lanes", &v) && v > 0) want_lanes = (size_t)v;
-        const size_t C = smexp_chunk(want_lanes, T);      // path_ranges.hpp
-        // chunks: at most ceil(len / C) per segment, i.e. <= T / C + (nonempty segments); the tail of them empty
-        const size_t nlanes = T == 0 ? 0 : std::min(T, T / C + std::min(S, T));
-        size_t mem_free = 0, mem_total = 0;
-        HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
-        // window width: as pai_ct_multiexp, with the table cost of a base amortised over its T / N terms
-        int wbits = 2;
-        {
-            double best = 1e300;
-            const double uses = N ? std::max(1.0, (double)T / (double)N) : 1.0;
-            for (int w = 2; w <= 7; ++w) {
-                const double tb = (double)N * nsigns * (double)((size_t)1 << w) * 2.0 * pnl * 4.0;
-                if (w > 2 && tb > (double)mem_total / 16.0) break;
-                const double cost = (double)((ebits_max + w - 1) / w) + (double)nsigns * (double)(((size_t)1 << w) - 2) / uses;
-                if (cost < best) { best = cost; wbits = w; }
-            }
-            if (long long v; knob_tune("mexp_wbits", &v) && v >= 1 && v <= 8) wbits = (int)v;
-        }
-        const size_t table_bytes = N * nsigns * ((size_t)1 << wbits) * 2 * (size_t)pnl * 4;
-        const size_t part_bytes = nlanes * (size_t)pk->ct_words * 4;
-        if (T && (table_bytes > mem_total / 8 ||
-                  table_bytes + part_bytes > mem_free + pk->mexp_table.bytes + pk->mexp_partial.bytes))
-            throw PaiError(PAI_E_UNSUPPORTED, "power tables of this sparse product do not fit the device");
-        // plan scratch: clean offsets [S + 1], chunk starts per segment [S + 1], first term per chunk [nlanes + 1]
-        pk->smexp_plan.ensure((2 * (S + 1) + nlanes + 1) * sizeof(int64_t));
-        int64_t* clean = pk->smexp_plan.as<int64_t>();
-        int64_t* cstart = clean + (S + 1);
-        int64_t* coff = cstart + (S + 1);
-        int* status = status_word(pk, s);
-        {
-            OrderScope order_(pk->order, s);
-            hipLaunchKernelGGL(k_smexp_offsets, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, d_offsets, (int)S, (int64_t)T, clean, status);
-            HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_seg_chunk_scan, dim3(1), dim3(SEG_PLAN_THREADS), 0, s, clean, (int)S, (int64_t)C, cstart);
-            HIP_CHECK(hipGetLastError());
-            if (nlanes) {
-                pk->mexp_table.ensure(table_bytes);
-                pk->mexp_partial.ensure(part_bytes);
-                const int eg = (int)std::min<size_t>((nlanes + 1 + 255) / 256, 1024);
-                hipLaunchKernelGGL(k_seg_chunk_expand, dim3(eg), dim3(256), 0, s, clean, cstart, (int)S, (int64_t)C, coff, nlanes);
-                HIP_CHECK(hipGetLastError());
-                SmexpArgs A;
-                A.base = d_base; A.coff = coff; A.status = status; A.nbases = (int)N;
-                if (digit) {
-                    MexpPadicParams Q;
-                    Q.nctx = pk->nmod.d_ctx;
-                    Q.nm1 = pk->d_nm1;
-                    Q.nsq = pk->d_nsq29;
-                    Q.kdig = pk->d_ct_kdig;
-                    Q.one_dig = pk->d_one_dig;
-                    Q.mscratch = reinterpret_cast<uint4*>(pk->d_mscratch);
-                    Q.table = pk->mexp_table.as<uint4>();
-                    Q.nd = pk->ct_nd;
-                    Q.ct_words = pk->ct_words;
-                    Q.R = 1; Q.K = (int)N; Q.M = 1; Q.chunk = (int)C; Q.nsigns = nsigns;
-                    Q.e_words = e_words;
-                    Q.ebits_max = ebits_max;
-                    Q.by_rows = 0;
-                    Q.wbits = wbits;
-                    if (N) {
-                        const size_t tl = N * nsigns, tiles = (tl + BLOCK_THREADS - 1) / BLOCK_THREADS;
-                        const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
-                        ScopedKernelTimer t("k_mexp_table", s);
-                        launcher(padic_enc_ops(pnl), &PadicEncOps::mexp_table, "no multi-exponentiation kernel for this limb count")(
-                            s, grid, Q, d_ct, d_ct_inv, (int)tl);
-                        t.stop();
-                        HIP_CHECK(hipGetLastError());
-                    }
-                    {
-                        const size_t tiles = (nlanes + BLOCK_THREADS - 1) / BLOCK_THREADS;
-                        const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
-                        ScopedKernelTimer t("k_smexp", s);
-                        launcher(padic_enc_ops(pnl), &PadicEncOps::smexp, "no multi-exponentiation kernel for this limb count")(
-                            s, grid, Q, A, d_e, d_sign, pk->mexp_partial.as<uint32_t>(), (int)nlanes);
-                        t.stop();
-                        HIP_CHECK(hipGetLastError());
-                    }
-                } else {
-                    MexpParams P;
-                    P.R = 1; P.K = (int)N; P.M = 1; P.chunk = (int)C; P.nsigns = nsigns;
-                    P.e_words = e_words; P.ebits_max = ebits_max; P.wbits = wbits; P.w32 = pk->ct_words;
-                    if (N) {
-                        const size_t tl = N * nsigns;
-                        ScopedKernelTimer t("k_mexp_table", s);
-                        lg->mexp_table(s, grid_for(lg, tl, pk->dev.ncu), pk->msq.d_ctx, d_ct, d_ct_inv, pk->ct_words, pk->mexp_table.as<uint32_t>(),
-                                       (int)tl, nsigns, wbits);
-                        t.stop();
-                        HIP_CHECK(hipGetLastError());
-                    }
-                    {
-                        ScopedKernelTimer t("k_smexp", s);
-                        lg->smexp(s, grid_for(lg, nlanes, pk->dev.ncu), pk->msq.d_ctx, P, A, pk->mexp_table.as<uint32_t>(), d_e, d_sign,
-                                  pk->mexp_partial.as<uint32_t>(), (int)nlanes);
-                        t.stop();
-                        HIP_CHECK(hipGetLastError());
-                    }
-                }
-            }
-            order_.done();
-        }
-        // the partials of segment s are rows cstart[s] .. cstart[s + 1] - 1, in the wire form (tag 0), all at shift 0
-        segment_prod_locked(pk, s, nlanes ? pk->mexp_partial.as<uint32_t>() : nullptr, nlanes, 0, nullptr, nullptr, cstart, S, d_out);
+        sparse_multiexp_locked(pk, (hipStream_t)stream, d_ct, d_ct_inv, N, d_base, d_e, e_words, ebits_max, d_sign, T, d_offsets, S, d_out);
     });
 }
 

@@ -23,6 +23,7 @@
 #include "kernels_pack.hpp"
 #include "kernels_declat.hpp"
 #include "kernels_crt_lift.hpp"
+#include "kernels_open_fold.hpp"
 
 using namespace pai;
 using hbn::Limbs;
@@ -385,12 +386,16 @@ struct ScopedKernelTimer {
 //                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns),
 //                                  padic_kara_red (36-limb decrypt: quotient products of the Montgomery reductions schoolbook, kernel mode PADIC_LDS_KM),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
-//                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch)
+//                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch),
+//                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
 //                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels),
 //                                  quantize_blocks (workgroups pai_fp_quantize aims at; default 4 per CU),
-//                                  rrec_grid (most workgroups per prime of k_rrec_a: a small batch then walks the tile loop)
+//                                  rrec_grid (most workgroups per prime of k_rrec_a: a small batch then walks the tile loop),
+//                                  open_chunk (elements per lane of pai_opening_fold; default: smexp_chunk's rule), open_wbits (window of
+//                                  k_open_fold's chain modulo n, 1 .. 4), open_grid (most workgroups of k_open_fold),
+//                                  open_block_rows (most rows of a row block of pai_opening_fold: forces the halving of blocks)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -529,6 +534,11 @@ struct pai_pubkey {
     mutable DevBuf pow2_expo;          // one-bit exponents of pai_ct_pow2's digit-engine path
     mutable DevBuf mexp_table, mexp_partial;   // power tables and partial products of pai_ct_multiexp (and pai_ct_sparse_multiexp)
     mutable DevBuf smexp_plan;                 // segment offsets and chunk plan of pai_ct_sparse_multiexp
+    // pai_opening_fold (dispatch_open_fold.hpp): segment starts, identity term list and the chunk plan's copy; power tables of k_open_fold;
+    // per-chunk parts (B, M, 1 + n M); per-segment rows (B_s, 1 + n M_s, B_s^n) and the composition route's widened rows.  open_mu
+    // serialises the calls (taken before pk->mu, never under it): the stages of one call run through several locked sections
+    mutable DevBuf open_plan, open_table, open_parts, open_rows, open_wide;
+    mutable std::mutex open_mu;
     mutable DevBuf seg_partial, seg_plan;      // chunk partials and chunk plans of pai_ct_segment_prod
     mutable DevBuf pack_plan;                  // member list of pai_ct_pack (rows, steps, chain offsets)
     mutable DevBuf quant_acc;                  // limb sums of pai_fp_quantize (four 64-bit words per column / segment)
@@ -1207,6 +1217,11 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     pk->mexp_table.release();
     pk->mexp_partial.release();
     pk->smexp_plan.release();
+    pk->open_plan.release();
+    pk->open_table.release();
+    pk->open_parts.release();
+    pk->open_rows.release();
+    pk->open_wide.release();
     pk->seg_partial.release();
     pk->seg_plan.release();
     pk->pack_plan.release();
@@ -1242,6 +1257,8 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
 int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
     return guarded([&] {
         require(pk != nullptr, "pk is NULL");
+        // open_mu first (the lock order of pai_opening_fold): a fold drops pk->mu between its stages and keeps using the open_* buffers
+        std::lock_guard<std::mutex> open_lk(pk->open_mu);
         std::lock_guard<std::mutex> lk(pk->mu);
         DeviceScope scope_(pk->device);
         HIP_CHECK(hipDeviceSynchronize());                     // nothing in flight may still read the tables / scratch
@@ -1265,6 +1282,11 @@ int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
         pk->mexp_table.release();
         pk->mexp_partial.release();
         pk->smexp_plan.release();
+        pk->open_plan.release();
+        pk->open_table.release();
+        pk->open_parts.release();
+        pk->open_rows.release();
+        pk->open_wide.release();
         pk->seg_partial.release();
         pk->seg_plan.release();
         pk->pack_plan.release();
@@ -1400,6 +1422,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_pack.hpp"
 #include "dispatch_encrypt_crt.hpp"
 #include "dispatch_recover.hpp"
+#include "dispatch_open_fold.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

@@ -212,6 +212,15 @@ static size_t smexp_chunk(size_t want_lanes, size_t terms) {
     return std::max<size_t>(1, (terms + want_lanes - 1) / std::max<size_t>(1, want_lanes));
 }
 
+// ---- batch verification of openings (dispatch_open_fold.hpp) ------------------------------------------------------------------------
+// pai_opening_fold has no batch-size switch of its own: the route is the key's (k_open_fold where the digit engine serves it,
+// PAI_DISABLE=open_fold: the composition of three sparse products on every key), and its last stage is pai_ct_mul's ranges above.
+// PAI_TUNE open_chunk: elements per lane (>= 1; tests force 1 / 2 / 3; default: smexp_chunk's rule — the fold runs on the chunk plan
+// of the ciphertexts' sparse product); open_wbits: window of k_open_fold's chain modulo n (1 .. 4, default 2; measured 61.3 / 39.9 /
+// 35.9 / 38.3 ms per 2^20 rows at 1 / 2 / 3 / 4 bits, 2048-bit keys: DESIGN section 2.8c); open_grid: most workgroups of k_open_fold.
+// open_block_rows (test hook): most rows of a row block, which forces the halving that a table too large for the device causes.
+// The API's default segmentation reads path_edges(2) — the first switch point of ct x pt — through pai_path_edges.
+
 // ---- packed ciphertexts -------------------------------------------------------------------------------------------------------------
 // pai_ct_pack on keys the digit engine serves: from this many OUTPUT rows (chains) on, one chain per lane on digit pairs
 // (k_ct_pack_padic); below, the k_segprod levels, which cut a chain into chunks and so fill the device with few chains.  A lane's

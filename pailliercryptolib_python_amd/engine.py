@@ -13,7 +13,7 @@ import ctypes as C
 import os
 import threading
 import weakref
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -443,6 +443,34 @@ class PublicKeyHandle:
         _native.check(self.lib.pai_ct_sparse_multiexp(self.h, _ptr(ct), _ptr(ct_inv), ct.shape[0], _ptr(base), _ptr(e), e.shape[1],
                                                       int(ebits_max), _ptr(sign), T, _ptr(offsets), S, _ptr(out), _stream(self.device)))
         return out
+
+    def opening_fold(self, ct: torch.Tensor, m: torch.Tensor, r: torch.Tensor, e: torch.Tensor, ebits: int,
+                     seg_len: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The two sides of the batch test of openings per segment of seg_len consecutive rows (pai_opening_fold):
+        lhs[s] = prod ct_i^(e_i) mod n^2 and rhs[s] = (1 + n sum e_i m_i) (prod r_i^(e_i))^n mod n^2, both [S, ct_words] in the wire
+        form, and an int32 device word whose bit 0 says that some segment's product of r is not a unit modulo n (its rhs row then
+        proves nothing).  ct [N, ct_words]; m, r [N, n_words]; e int32 [N, ew] coefficients of at most `ebits` bits, 1 <= ew <= 8."""
+        self._chk(ct, self.ct_words, "ct")
+        self._chk(m, self.n_words, "m")
+        self._chk(r, self.n_words, "r")
+        n = ct.shape[0]
+        if m.shape[0] != n or r.shape[0] != n:
+            raise ValueError("opening_fold: ct, m and r differ in length")
+        if e.dtype != torch.int32 or e.dim() != 2 or e.shape[0] != n or not e.is_contiguous() or e.device != self.device:
+            raise ValueError(f"e: expected contiguous int32 [N, ew] on {self.device}")
+        seg_len = int(seg_len)
+        S = (n + seg_len - 1) // seg_len if seg_len >= 1 else 0
+        lhs, rhs, flag = self.empty_ct(S), self.empty_ct(S), self.new_flag()
+        _native.check(self.lib.pai_opening_fold(self.h, _ptr(ct), _ptr(m), _ptr(r), n, _ptr(e), e.shape[1], int(ebits), seg_len,
+                                                _ptr(lhs), _ptr(rhs), _ptr(flag), _stream(self.device)))
+        return lhs, rhs, flag
+
+    def path_edges(self, op: int) -> list:
+        """The batch sizes at which the path of `op` may change on this handle's device (pai_path_edges), ascending."""
+        buf = (C.c_size_t * 16)()
+        cnt = C.c_int(0)
+        _native.check(self.lib.pai_path_edges(self.h, int(op), buf, 16, C.byref(cnt)))
+        return [int(buf[i]) for i in range(min(cnt.value, 16))]
 
     def ct_multiexp(self, ct: torch.Tensor, ct_inv: Optional[torch.Tensor], R: int, K: int, M: int, e: torch.Tensor,
                     ebits_max: int, sign: Optional[torch.Tensor]) -> torch.Tensor:

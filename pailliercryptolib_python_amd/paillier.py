@@ -18,6 +18,7 @@ obfuscator randomness, ``decrypt_to_numpy``, ``PaillierEncryptedNumber.words``.
 from __future__ import annotations
 
 import os
+import secrets
 from typing import Callable, List, Optional, Tuple, Union
 
 import numpy as np
@@ -112,24 +113,24 @@ class PaillierPublicKey:
         return _packed.encrypt_packed(self, values, exponent=exponent, value_bits=value_bits, slot_bits=slot_bits, slots=slots,
                                       apply_obfuscator=apply_obfuscator, r=r, _encrypt_words=_encrypt_words)
 
-    def verify_opening(self, x, opening) -> np.ndarray:
-        """Extension: checks openings of the ciphertexts of `x` (a PaillierEncryptedNumber or PaillierPackedNumber) with the public
-        key alone: element i is True iff (1 + m_i n) r_i^n mod n^2 is ciphertext i, bit for bit — one standard-scheme encryption
-        per element on the device.  `opening` is a PaillierOpening (its exponents are compared too) or a pair (m_ints, r_ints).
-        m_i >= n, r_i = 0 and r_i >= n make element i False, never an exception; a length mismatch is a ValueError."""
+    def _opening_operands(self, x, opening, who: str):
+        """The argument handling and range checks shared by verify_opening and verify_openings: (ok, words, m_t, r_t, bad) — ok:
+        host bool [rows], False where the exponents differ or a value of a pair (m, r) does not fit; words: the ciphertext rows;
+        m_t, r_t: the residues on the device with every row outside m < n, 0 < r < n replaced by (0, 1); bad: those rows (device
+        bool), None for an empty batch."""
         pub = self.pubkey
         ct = x.ciphertext()
         if ct.public_key._n != self.n:
-            raise ValueError("PaillierPublicKey.verify_opening: public key mismatch")
+            raise ValueError(f"PaillierPublicKey.{who}: public key mismatch")
         words = ct.words
         rows = int(words.shape[0])
         h = pub.handle
         ok = np.ones(rows, dtype=bool)
         if isinstance(opening, PaillierOpening):
             if opening.public_key.n != self.n:
-                raise ValueError("PaillierPublicKey.verify_opening: the opening belongs to another key")
+                raise ValueError(f"PaillierPublicKey.{who}: the opening belongs to another key")
             if len(opening) != rows:
-                raise ValueError(f"PaillierPublicKey.verify_opening: {rows} ciphertexts, {len(opening)} openings")
+                raise ValueError(f"PaillierPublicKey.{who}: {rows} ciphertexts, {len(opening)} openings")
             m_t, r_t = opening._words(h.device)
             expo = getattr(x, "_expo", None)
             if expo is not None and opening._expo is not None:
@@ -138,20 +139,20 @@ class PaillierPublicKey:
             try:
                 m_in, r_in = opening
             except (TypeError, ValueError):
-                raise TypeError("PaillierPublicKey.verify_opening: expected a PaillierOpening or a pair (m, r)") from None
+                raise TypeError(f"PaillierPublicKey.{who}: expected a PaillierOpening or a pair (m, r)") from None
             ms = [int(m_in)] if isinstance(m_in, (int, np.integer)) else [int(v) for v in m_in]
             rs = [int(r_in)] if isinstance(r_in, (int, np.integer)) else [int(v) for v in r_in]
             if len(ms) != rows or len(rs) != rows:
-                raise ValueError(f"PaillierPublicKey.verify_opening: {rows} ciphertexts, {len(ms)} values of m, {len(rs)} of r")
+                raise ValueError(f"PaillierPublicKey.{who}: {rows} ciphertexts, {len(ms)} values of m, {len(rs)} of r")
             if rows == 0:
-                return ok
+                return ok, words, None, None, None
             # values that do not fit a row of words are False already; the row that stands in for them is checked like any other
             fit = np.array([0 <= m < self.n and 0 < r < self.n for m, r in zip(ms, rs)], dtype=bool).reshape(rows)
             ok &= fit
             m_t = engine.to_device_words(engine.ints_to_words([m if f else 0 for m, f in zip(ms, fit)], h.n_words), h.device)
             r_t = engine.to_device_words(engine.ints_to_words([r if f else 1 for r, f in zip(rs, fit)], h.n_words), h.device)
         if rows == 0:
-            return ok
+            return ok, words, None, None, None
         # range checks on the device: the kernels take residues, and (m + n, r) or (m, r + n) must not pass for (m, r)
         n_w = torch.from_numpy(engine.int_to_words(self.n, h.n_words).astype(np.int64)).to(h.device)
         bad_r = _bindings._rows_not_in_1_n(r_t, n_w)
@@ -163,9 +164,95 @@ class PaillierPublicKey:
             one[0, 0] = 1
             m_t = m_t * keep
             r_t = r_t * keep + one * (1 - keep)
-        again = pub.standard_twin().encrypt_words(m_t.contiguous(), True, r_t.contiguous())
+        return ok, words, m_t, r_t, bad
+
+    def verify_opening(self, x, opening) -> np.ndarray:
+        """Extension: checks openings of the ciphertexts of `x` (a PaillierEncryptedNumber or PaillierPackedNumber) with the public
+        key alone: element i is True iff (1 + m_i n) r_i^n mod n^2 is ciphertext i, bit for bit — one standard-scheme encryption
+        per element on the device.  `opening` is a PaillierOpening (its exponents are compared too) or a pair (m_ints, r_ints).
+        m_i >= n, r_i = 0 and r_i >= n make element i False, never an exception; a length mismatch is a ValueError."""
+        ok, words, m_t, r_t, bad = self._opening_operands(x, opening, "verify_opening")
+        if bad is None:
+            return ok
+        again = self.pubkey.standard_twin().encrypt_words(m_t.contiguous(), True, r_t.contiguous())
         same = (again == words).all(dim=1) & ~bad
         return ok & same.cpu().numpy()
+
+    def verify_openings(self, x, opening, *, security_bits: int = 128, segment: Optional[int] = None, _coefficients=None) -> np.ndarray:
+        """Extension: verify_opening for a batch at one exponentiation by n per SEGMENT instead of one per element (the
+        small-exponent batch test by random linear combinations).  Same arguments, errors and result shape as verify_opening.
+        With secret coefficients e_i < 2^security_bits drawn after the openings are fixed, a segment of consecutive elements passes
+        iff  prod ct_i^(e_i) == (1 + n sum e_i m_i) (prod r_i^(e_i))^n  (mod n^2)  and prod r_i^(e_i) is a unit modulo n
+        (pai_opening_fold).  Element i is False when its exponents differ, when m_i >= n, r_i = 0 or r_i >= n, or when its
+        ciphertext row is not a canonical residue (>= n^2); such rows enter the fold as the neutral triple (1, 0, 1).  The
+        other elements of a passing segment are True.  The rows of a failing segment — of every segment when a product of r is
+        not a unit — are checked one by one, and the answer there is verify_opening's.
+
+        What a True certifies.  Valid openings always pass.  The PLAINTEXTS are certified: if some m_i of a passing segment
+        is not the plaintext of ciphertext i, the segment passes with probability at most 2^-security_bits over the
+        coefficients, also against a prover who knows p and q; with the chance of a coefficient that is 0 the error is at most
+        2 * 2^-security_bits per element.  The RANDOMNESS is certified only up to factors of small order: Enc(m, n - r) =
+        -Enc(m, r) because n is odd, so a claimed (m, n - r) passes exactly when the coefficients of such elements sum to an even
+        number — half the time.  Use verify_opening where r itself must be pinned; this method is the check verifiable
+        decryption needs.
+
+        security_bits: 32 .. 256 and below bitlen(n) / 2 - 1 (a coefficient must stay below both primes).  segment: elements
+        per segment; default: as many segments as the final exponentiation still serves on its small-batch route (the first
+        switch point of pai_path_edges for ct x pt).  _coefficients: the e_i as Python ints — for tests only; fixed or published
+        coefficients certify nothing.  Runs on the key's home device."""
+        lam = int(security_bits)
+        if not 32 <= lam <= 256 or not lam < self.n.bit_length() / 2 - 1:
+            raise ValueError("PaillierPublicKey.verify_openings: security_bits must lie in 32 .. 256 and below bitlen(n) / 2 - 1")
+        if segment is not None and int(segment) < 1:
+            raise ValueError("PaillierPublicKey.verify_openings: segment must be at least 1")
+        ok, words, m_t, r_t, bad = self._opening_operands(x, opening, "verify_openings")
+        if bad is None:
+            return ok
+        pub = self.pubkey
+        h = pub.handle
+        rows = int(words.shape[0])
+        # a row that is not a canonical residue is False as in verify_opening (which compares bit for bit); the fold would reduce it
+        nsq_w = torch.from_numpy(engine.int_to_words(self.nsquare, h.ct_words).astype(np.int64)).to(h.device)
+        words = words if words.device == h.device else words.to(h.device)
+        bad = bad | (_bindings._rows_not_in_1_n(words, nsq_w) & ((words != 0).any(dim=1)))
+        ct_t = words
+        if bool(bad.any()):
+            keep = (~bad).to(words.dtype).unsqueeze(1)
+            one_c = torch.zeros_like(words[:1])
+            one_c[0, 0] = 1
+            one_r = torch.zeros_like(r_t[:1])
+            one_r[0, 0] = 1
+            ct_t = words * keep + one_c * (1 - keep)
+            m_t = m_t * keep
+            r_t = r_t * keep + one_r * (1 - keep)
+        ew = (lam + 31) // 32
+        if _coefficients is not None:
+            es = [int(v) for v in _coefficients]
+            if len(es) != rows or any(not 0 <= v < (1 << lam) for v in es):
+                raise ValueError("PaillierPublicKey.verify_openings: _coefficients must be one integer below 2^security_bits per element")
+            e_np = engine.ints_to_words(es, ew)
+        else:
+            e_np = np.frombuffer(secrets.token_bytes(4 * ew * rows), dtype="<u4").reshape(rows, ew).copy()
+            if lam % 32:
+                e_np[:, ew - 1] &= np.uint32((1 << (lam % 32)) - 1)
+        e_t = engine.to_device_words(e_np, h.device)
+        if segment is None:
+            edges = h.path_edges(2)
+            most = max(1, min(edges)) if edges else 1
+            seg = -(-rows // min(rows, most))
+        else:
+            seg = int(segment)
+        lhs, rhs, flag = pub.opening_fold_words(ct_t.contiguous(), m_t.contiguous(), r_t.contiguous(), e_t, lam, seg)
+        seg_ok = (lhs == rhs).all(dim=1)
+        if int(flag.item()) & 1:
+            seg_ok = torch.zeros_like(seg_ok)
+        good = ~bad
+        res = seg_ok.repeat_interleave(seg)[:rows] & good
+        redo = torch.nonzero(~seg_ok.repeat_interleave(seg)[:rows] & good, as_tuple=False).reshape(-1)
+        if redo.numel():
+            again = pub.standard_twin().encrypt_words(m_t[redo].contiguous(), True, r_t[redo].contiguous())
+            res[redo] = (again == words[redo]).all(dim=1)
+        return ok & res.cpu().numpy()
 
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
