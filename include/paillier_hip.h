@@ -20,6 +20,18 @@
  *    non-invertible inputs; pai_ct_invert_async + pai_pubkey_status is the asynchronous form), pai_pubkey_status,
  *    pai_pubkey_trim and pai_ct_pow2 without a hint return after their stream work has completed; everything else,
  *    pai_decrypt and pai_modexp_fixed (its host exponent is copied to pinned staging) included, is asynchronous;
+ *  - memory contract (held by tests/test_gpu_memory_contract.py).  Alignment: a device pointer needs the alignment of its C
+ *    type and no more — 4 bytes for uint32_t / int32_t rows, 8 for double / int64_t / uint64_t, 1 for uint8_t; row r of a batch
+ *    is a valid operand whatever the row length (rows of 34 or 102 words are not 16-byte multiples).  Kernels that move rows as
+ *    16-byte vectors test the address at run time and fall back to word accesses.  Extent: a call reads its operands, writes the
+ *    outputs it documents — N rows, ceil(N / k) rows, S rows, one flag word — and nothing else: no word before or behind an
+ *    output, no word of an input, whatever lies next to them.  Aliasing: an output may be EXACTLY an operand (same address, same
+ *    extent) where the call says so.  The calls that state an aliasing rule below (pai_ct_add, pai_ct_mont_mul, pai_ct_add_aligned*,
+ *    pai_ct_addn, pai_ct_add_plain, pai_ct_mul*, pai_ct_invert*, pai_ct_scan, pai_ct_pack*, pai_buf_slice, pai_buf_rotate,
+ *    pai_modmul) answer any other overlap of the output's byte range with the named operand's byte range with PAI_E_INVALID and
+ *    launch nothing; in every other call, and for the small operands of these (shifts, entry constants), an output that overlaps
+ *    an operand is undefined.  In particular a broadcast row (b_bcast != 0) may be the output only when N == 1: with N > 1 other
+ *    waves still load it while output row 0 is stored;
  *  - a call never changes the calling thread's current HIP device (it is restored on return);
  *  - there is NO CPU fallback: without a usable gfx950 device key creation fails with
  *    PAI_E_NODEVICE.
@@ -90,7 +102,8 @@ int pai_ct_mul_host(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
  * ipclPlainText / ipclCipherText __getitem__ with a slice and rotate (bindings/ipcl_bindings_classes.cpp:224-262,328-366;
  * rotate is what the reference's reductions are built from, ipcl_python.py:810-827).  Rows of `row_words` words.
  * slice:  d_out[i] = d_src[start + i * step] for i < count (step >= 1);  rotate:  d_out[i] = d_src[(i + shift) mod N]
- * (any sign of shift; d_out must not alias d_src).  Asynchronous on `stream`. */
+ * (any sign of shift).  d_out must not overlap the rows the call reads (PAI_E_INVALID; slice: rows start .. start + (count - 1) step).
+ * Asynchronous on `stream`. */
 int pai_buf_slice(int device, const uint32_t* d_src, int row_words, size_t start, size_t count, size_t step, uint32_t* d_out,
                   void* stream);
 int pai_buf_rotate(int device, const uint32_t* d_src, int row_words, size_t N, long long shift, uint32_t* d_out, void* stream);
@@ -156,7 +169,8 @@ int pai_raw_encrypt(const pai_pubkey* pk, const uint32_t* d_m, size_t N, uint32_
  * and :365-381 / classes.cpp:318-321 multiply the two ciphertexts; in ONE pass here:
  * d_out[i] = d_ct[i] * (1 + d_m[i] * n) mod n^2, wire form in and out (round 6: the reference's BM_Add_CTPT is two launches and an
  * intermediate array otherwise).  d_m: [N][n_words] residues < n (already encoded AT the ciphertext's exponents: pai_fp_encode_at).
- * d_out may alias d_ct.  Small batches run on the latency geometry (three sequential products), others on lane groups. */
+ * d_out may alias d_ct (exactly; it must not overlap d_m).  Small batches run on the latency geometry (three sequential products),
+ * others on lane groups. */
 int pai_ct_add_plain(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_m, size_t N, uint32_t* d_out, void* stream);
 
 /* ipclPublicKey.encrypt(pt, make_secure=true) — classes.cpp:53-60 with the randomness made explicit.
@@ -216,7 +230,8 @@ int pai_obfuscate_crt(pai_privkey* sk, uint32_t* d_ct, const uint32_t* d_r, size
 int pai_privkey_crt_table_info(const pai_privkey* sk, size_t* table_bytes, int* window_bits, int* windows);
 
 /* ipclCipherText.__add__(ct, ct) — classes.cpp:318-321: d_out[i] = d_a[i] * d_b[i] mod n^2.
- * b_bcast != 0: d_b holds one ciphertext used for every i (size-1 broadcast).  d_out may alias d_a.
+ * b_bcast != 0: d_b holds one ciphertext used for every i (size-1 broadcast).  d_out may alias d_a, or d_b when b_bcast == 0 or
+ * N == 1 (exactly: the memory contract above; a broadcast row inside a longer output is PAI_E_INVALID).
  * Operands are residues modulo n^2 (as everywhere in this ABI); the result is the canonical residue.  (Batches beyond the
  * small-batch range run one most-significant-limb-first product per element, csrc/mont_msb.hpp, which would also accept rows that
  * are not reduced; the small-batch route does not promise that.) */
@@ -224,13 +239,15 @@ int pai_ct_add(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, i
                uint32_t* d_out, void* stream);
 
 /* ipclCipherText.__mul__(ct, pt) — classes.cpp:324-325: d_out[i] = d_ct[i] ^ e_i mod n^2, e_i >= 0.
- * d_e: [N][e_words] (or one row if e_bcast); ebits_max bounds the bit length of every e_i. */
+ * d_e: [N][e_words] (or one row if e_bcast); ebits_max bounds the bit length of every e_i.  d_out may alias d_ct (exactly: every
+ * path reads row i before it stores row i, with per-element and with broadcast exponents); it must not overlap d_e. */
 int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, int e_words, int ebits_max,
                int e_bcast, size_t N, uint32_t* d_out, void* stream);
 
 /* Replaces the per-element gmpy2.invert of PaillierEncryptedNumber.__invert_ct (ipcl_python.py:272-276):
  * d_out[i] = d_ct[i]^-1 mod n^2 (batched: simultaneous inversion as a product tree + one extended GCD per top-level
- * product).  Synchronous; fails with PAI_E_INVALID if some ciphertext shares a factor with n.  d_out may alias d_ct. */
+ * product).  Synchronous; fails with PAI_E_INVALID if some ciphertext shares a factor with n.  d_out may alias d_ct
+ * (exactly; a partial overlap is PAI_E_INVALID, here and in the two forms below). */
 int pai_ct_invert(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, uint32_t* d_out, void* stream);
 /* The same work without the synchronisation: returns as soon as the kernels are queued on `stream`; a non-invertible input
  * sets bit 0 of the handle's sticky status word (pai_pubkey_status below) instead of failing the call. */
@@ -245,7 +262,9 @@ int pai_ct_invert_flag(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, uin
  * (base-2 fixed-point exponents, int32 on the device); the operand with the LOWER exponent is raised first:
  * d_out[i] = delta_i > 0 ? d_a[i] * d_b[i]^(2^delta_i) : d_a[i]^(2^-delta_i) * d_b[i]   (mod n^2).
  * The result's exponent is max(exponent(a_i), exponent(b_i)) (the caller's bookkeeping).  One pass over the data instead
- * of two pai_ct_pow2 passes and a pai_ct_add.  b_bcast != 0: one ciphertext b for every i.  d_out may alias d_a or d_b. */
+ * of two pai_ct_pow2 passes and a pai_ct_add.  b_bcast != 0: one ciphertext b for every i.  d_out may alias d_a, or d_b
+ * when b_bcast == 0 or N == 1 (exactly; a broadcast row inside a longer output is PAI_E_INVALID, as for pai_ct_add; the same holds
+ * for pai_ct_add_aligned_host and pai_ct_add_aligned_dom). */
 int pai_ct_add_aligned(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, int b_bcast, const int32_t* d_delta,
                        size_t N, uint32_t* d_out, void* stream);
 
@@ -256,7 +275,8 @@ int pai_ct_add_aligned(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t
  * be NULL) to int32 [N] squaring counts >= 0 — the caller raises every operand to the per-element maximum exponent of the sum.
  * Lazy-domain bookkeeping as for pai_ct_mont_mul: operand 0 holds x R^tag0, the others x R^tag, the result x R^dom_out (any tags
  * with |.| small: wire form is 0; tag0 + (k-1)(tag-1) is the tag that costs no extra product; a raised operand 0 needs tag0 ==
- * tag).  k - 1 Montgomery products per element (+1 per raised operand and per squaring), one store.  d_out may alias an operand.
+ * tag).  k - 1 Montgomery products per element (+1 per raised operand and per squaring), one store.  d_out may alias an operand (exactly: any
+ * one of the k; a partial overlap with any of them is PAI_E_INVALID).
  * Asynchronous on `stream`. */
 int pai_ct_addn(const pai_pubkey* pk, const uint32_t* const* h_ops, const int32_t* const* h_raise, int k, int tag0, int tag,
                 int dom_out, size_t N, uint32_t* d_out, void* stream);
@@ -267,7 +287,7 @@ int pai_ct_addn(const pai_pubkey* pk, const uint32_t* const* h_ops, const int32_
  * pai_ct_add needs two (or the 1.4 x dearer most-significant-limb-first product): operands with tags ka, kb give ciphertext-addition with tag ka + kb - 1.  Multiplying by the
  * broadcast constant R^(1 + k' - k) mod n^2 (b_bcast != 0) moves a buffer from tag k to tag k', e.g. back to the wire
  * form before decryption, export or pickling — the bits at every boundary are those of CipherText::operator+
- * (classes.cpp:318-321).  d_out may alias d_a. */
+ * (classes.cpp:318-321).  d_out may alias d_a, or d_b when b_bcast == 0 or N == 1 (exactly, as for pai_ct_add). */
 int pai_ct_mont_mul(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, int b_bcast, size_t N, uint32_t* d_out,
                     void* stream);
 int pai_pubkey_mont_bits(const pai_pubkey* pk, int* bits);
@@ -319,7 +339,7 @@ int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, in
  * With raise_i = E_i - e_i and step_i = E_i - E_(i-1), E the running maximum of the exponents e, row i is the exponent-aligned sum
  * of its run's rows up to i.  d_ct: [N][ct_words] at domain tag `tag` (pai_ct_mont_mul; |tag|, |dom_out| <= 46); d_raise, d_step:
  * int32 [N] indexed by row, NULL = all 0; the step of a run's first row is ignored; both may be non-zero on one row.  seg_len must
- * divide N (PAI_E_INVALID otherwise); d_out: [N][ct_words], must not alias d_ct.  A negative raise or step counts as 0 and sets
+ * divide N (PAI_E_INVALID otherwise); d_out: [N][ct_words], must not overlap d_ct (PAI_E_INVALID).  A negative raise or step counts as 0 and sets
  * bit 4 of the handle's status word (pai_pubkey_status).  Cost: 1 + [tag != 1] + [dom_out != 1] Montgomery products per row plus
  * one per squaring, when there are enough runs to give every lane group of the device one.  Fewer runs are cut into chunks
  * (PAI_TUNE scan_chunk: the chunk length): chunk totals, the scan of the totals (the same call on the handle's scratch, level by
@@ -404,7 +424,7 @@ int pai_fp_unpack(const pai_pubkey* pk, const uint32_t* d_m, size_t G, int slot_
                   void* stream);
 /* pai_ct_pack: packs N ciphertexts (equal exponents: the caller's bookkeeping) into G: d_out[g] = prod_j d_ct[g k + j]^(2^(b j))
  * mod n^2, an encryption of P_g, in the wire form (canonical residues, not re-randomised).  d_ct: [N][ct_words] at domain tag `tag`
- * (as pai_ct_segment_prod); d_out: [G][ct_words], must not alias d_ct.  One Horner chain acc <- acc^(2^b) * ct_j, j = k-1 ... 0,
+ * (as pai_ct_segment_prod); d_out: [G][ct_words], must not overlap d_ct (PAI_E_INVALID; pai_ct_pack_step too).  One Horner chain acc <- acc^(2^b) * ct_j, j = k-1 ... 0,
  * per output row — b squarings and one product per packed element.  Two routes with identical results: the level driver of
  * pai_ct_segment_prod (the member list is written on the device; synchronises `stream` once, like that call), and, for keys up to
  * 2048 bits, wire-form input and batches of more output rows than the pai_path_edges(op 4) edge, one chain per lane on base-n
@@ -462,7 +482,8 @@ int pai_scatter(int nshards, const int* devices, void* const* d_shards, const si
 /* ---- generic modular building blocks (arbitrary odd modulus up to 8192 bits) ------------------- */
 int pai_modulus_create(const uint32_t* h_m, int m_words, int device, pai_modulus** out);
 void pai_modulus_destroy(pai_modulus* m);
-/* out[i] = a[i] * b[i] mod M; rows of w32 words (w32 = ceil(bits(M)/32)) */
+/* out[i] = a[i] * b[i] mod M; rows of w32 words (w32 = ceil(bits(M)/32)).  d_out may alias d_a, or d_b when b_bcast == 0 or N == 1
+ * (exactly, as for pai_ct_add). */
 int pai_modmul(pai_modulus* m, const uint32_t* d_a, const uint32_t* d_b, int b_bcast, size_t N, uint32_t* d_out,
                void* stream);
 /* out[i] = base[i] ^ E mod M, E given on the HOST (wave-uniform exponent, fixed 5-bit window) */

@@ -8,6 +8,7 @@ int pai_ct_add(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, i
     return guarded([&] {
         require(pk && d_a && d_b && d_out, "NULL argument");
         if (N == 0) return;
+        require_out_ab(d_a, d_b, b_bcast, N, d_out, pk->ct_words);
         DeviceScope scope_(pk->device);
         g_last_times.clear();
         const ModSetup* L = lat_add_ctx(pk, N, false, lat_add_wire_scale(pk->key_bits));
@@ -39,6 +40,7 @@ static void add_aligned_common(const pai_pubkey* pk, const uint32_t* d_a, const 
                                size_t N, uint32_t* d_out, const uint32_t* d_entry, void* stream) {
     require(pk && d_a && d_b && d_delta && d_out, "NULL argument");
     if (N == 0) return;
+    require_out_ab(d_a, d_b, b_bcast, N, d_out, pk->ct_words);
     DeviceScope scope_(pk->device);
     // wire-form operands (no entry constant): small batches on the latency geometry — the kernel enters and leaves the
     // Montgomery domain itself, so the geometry's R does not show in the result
@@ -65,7 +67,8 @@ int pai_ct_add_aligned(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t
 int pai_ct_add_aligned_host(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d_b, int b_bcast, const int32_t* h_delta,
                             size_t N, uint32_t* d_out, void* stream) {
     return guarded([&] {
-        require(pk && h_delta, "NULL argument");
+        require(pk && h_delta && d_a && d_b && d_out, "NULL argument");
+        if (N) require_out_ab(d_a, d_b, b_bcast, N, d_out, pk->ct_words);      // a refused call stages nothing
         const void* src[1] = {h_delta};
         const size_t len[1] = {N * sizeof(int32_t)};
         void* dp[1] = {nullptr};
@@ -87,6 +90,7 @@ int pai_ct_mont_mul(const pai_pubkey* pk, const uint32_t* d_a, const uint32_t* d
     return guarded([&] {
         require(pk && d_a && d_b && d_out, "NULL argument");
         if (N == 0) return;
+        require_out_ab(d_a, d_b, b_bcast, N, d_out, pk->ct_words);
         DeviceScope scope_(pk->device);
         g_last_times.clear();
         if (const ModSetup* L = lat_add_ctx(pk, N, true)) {
@@ -145,6 +149,9 @@ int pai_ct_addn(const pai_pubkey* pk, const uint32_t* const* h_ops, const int32_
         require(std::abs(2 - tag) <= RPOW_SPAN && std::abs(1 + dom_out - c_lo) <= RPOW_SPAN && std::abs(1 + dom_out - c_hi) <= RPOW_SPAN,
                 "pai_ct_addn: domain tags out of range");
         if (N == 0) return;
+        for (int j = 0; j < k; ++j)
+            require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, h_ops[j], N * (size_t)pk->ct_words * 4, true,
+                               "pai_ct_addn: d_out overlaps an operand (an output may be exactly an operand, nothing else)");
         DeviceScope scope_(pk->device);
         const uint32_t* rpow;
         {

@@ -112,6 +112,9 @@ int pai_ct_mul(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_e, 
         require(pk && d_ct && d_e && d_out, "NULL argument");
         require(e_words > 0 && ebits_max > 0 && ebits_max <= 32 * e_words, "bad exponent shape");
         if (N == 0) return;
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, true,
+                           "pai_ct_mul: d_out overlaps d_ct (an output may be exactly an operand, nothing else)");
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_e, (e_bcast ? 1 : N) * (size_t)e_words * 4, false, "pai_ct_mul: d_out overlaps d_e");
         DeviceScope scope_(pk->device);
         hipStream_t s = (hipStream_t)stream;
         g_last_times.clear();
@@ -213,7 +216,10 @@ int pai_ct_mul_host(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
                     uint32_t* d_out, void* stream) {
     const void* dp0 = nullptr;
     const int rc = guarded([&] {
-        require(pk && h_e && e_words > 0, "NULL argument");
+        require(pk && h_e && d_ct && d_out && e_words > 0, "NULL argument");
+        if (N)                                                                  // a refused call stages nothing
+            require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, true,
+                               "pai_ct_mul: d_out overlaps d_ct (an output may be exactly an operand, nothing else)");
         const void* src[1] = {h_e};
         const size_t len[1] = {(e_bcast ? 1 : N) * (size_t)e_words * 4};
         void* dp[1] = {nullptr};

@@ -273,6 +273,9 @@ int pai_ct_add_plain(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t*
     return guarded([&] {
         require(pk && d_ct && d_m && d_out, "NULL argument");
         if (N == 0) return;
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, true,
+                           "pai_ct_add_plain: d_out overlaps d_ct (an output may be exactly an operand, nothing else)");
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_m, N * (size_t)pk->n_words * 4, false, "pai_ct_add_plain: d_out overlaps d_m");
         DeviceScope scope_(pk->device);
         hipStream_t s = (hipStream_t)stream;
         g_last_times.clear();

@@ -110,11 +110,12 @@ static void ct_pack_body(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, i
     require(std::abs(tag) <= RPOW_SPAN - 2, "pai_ct_pack: domain tag out of range");
     require(N < ((size_t)1 << 31), "pai_ct_pack: too many rows for one call");
     if (N == 0) return;
+    const size_t G = (N + (size_t)count - 1) / (size_t)count;
+    require_no_overlap(d_out, G * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, false, "pai_ct_pack: d_out must not alias d_ct");
     std::lock_guard<std::mutex> lk(pk->mu);
     DeviceScope scope_(pk->device);
     hipStream_t s = (hipStream_t)stream;
     g_last_times.clear();
-    const size_t G = (N + (size_t)count - 1) / (size_t)count;
     if (pk->penc_nl != 0 && tag == 0 && N < ((size_t)1 << 28) && !knob_disabled("pack_padic") &&
         G >= pack_padic_min_rows((size_t)pk->dev.ncu) && ct_pack_padic_locked(pk, s, d_ct, N, step, count, G, d_out))
         return;

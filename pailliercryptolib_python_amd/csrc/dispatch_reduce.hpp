@@ -450,6 +450,8 @@ static int ct_invert_impl(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, 
     return guarded([&] {
         require(pk && d_ct && d_out, "NULL argument");
         if (N == 0) return;
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, true,
+                           "ct_invert: d_out overlaps d_ct (an output may be exactly an operand, nothing else)");
         std::lock_guard<std::mutex> lk(pk->mu);
         DeviceScope scope_(pk->device);
         hipStream_t s = (hipStream_t)stream;

@@ -78,7 +78,7 @@ int pai_ct_scan(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, i
         if (N == 0) return;
         require(seg_len > 0 && N % seg_len == 0, "pai_ct_scan: seg_len must divide N");
         require(d_ct && d_out, "NULL argument");
-        require(d_out != d_ct, "pai_ct_scan: d_out must not alias d_ct");
+        require_no_overlap(d_out, N * (size_t)pk->ct_words * 4, d_ct, N * (size_t)pk->ct_words * 4, false, "pai_ct_scan: d_out must not alias d_ct");
         std::lock_guard<std::mutex> lk(pk->mu);
         DeviceScope scope_(pk->device);
         g_last_times.clear();

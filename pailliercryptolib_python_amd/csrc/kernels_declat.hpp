@@ -224,7 +224,7 @@ PAI_DEV void pp_store(uint32_t* lds, int off, const uint32_t (&x)[G::NLL]) {
 // the reference's BM_Mul_CTPT): ONE modulus (s = n, the power modulo n^2) and the exponent of each element its own; exponent 0
 // gives 1.
 template <class G, class GC, bool VAR>
-PAI_DEV void pp_chain(const DecPPParams& P, const uint32_t* __restrict__ ct, uint32_t* __restrict__ u_out, int n, uint32_t* lds) {
+PAI_DEV void pp_chain(const DecPPParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* lds) {      // VAR: u_out may be ct (pai_ct_mul in place)
     static_assert(G::M1 && G::T == 64 && GC::T == 64 && GC::U == 1 && BLOCK_THREADS == 256, "one integer per wavefront, four waves per chain");
     constexpr int NLL = GC::NLL, U = GC::U;          // the chain's geometry; the exit (B2's tail) runs on G
     constexpr int GN = G::NLL, GU = G::U;
@@ -501,7 +501,7 @@ k_dec_a_pp(DecPPParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict_
 }
 template <class G, class GC>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
-k_ctmul_pp(DecPPParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict__ out /*[n][u_words]*/, int n) {
+k_ctmul_pp(DecPPParams P, const uint32_t* ct, uint32_t* out /*[n][u_words]*/, int n) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     pp_chain<G, GC, true>(P, ct, out, n, lds);
 }

@@ -260,9 +260,9 @@ k_modexp_fixed(const MontCtx* __restrict__ ctx, const uint32_t* __restrict__ bas
 // binary method; the multiply step is skipped when no element of the wave needs it.
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, PAI_LG_WAVES(G))
-k_modexp_var(const MontCtx* __restrict__ ctx, const uint32_t* __restrict__ base, int base_w32, int base_shift,
+k_modexp_var(const MontCtx* __restrict__ ctx, const uint32_t* base, int base_w32, int base_shift,
              const uint32_t* __restrict__ expo, int ew, int ebits_max, int exp_bcast,
-             uint32_t* __restrict__ out, int out_w32, int n, int keep_mont, int out_raw) {
+             uint32_t* out, int out_w32, int n, int keep_mont, int out_raw) {          // out may be base (pai_ct_mul in place)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     typename G::NM nm;
     load_modulus<G>(nm, ctx, lds);
@@ -347,9 +347,9 @@ struct VarWinCfg {
 
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, PAI_VARWIN_WAVES(G))
-k_modexp_var_win(const MontCtx* __restrict__ ctx, const uint32_t* __restrict__ base, int base_w32,
+k_modexp_var_win(const MontCtx* __restrict__ ctx, const uint32_t* base, int base_w32,
                  const uint32_t* __restrict__ expo, int ew, int ebits_max, int exp_bcast,
-                 uint32_t* __restrict__ out, int out_w32, int n, uint32_t* __restrict__ table, int wbits,
+                 uint32_t* out, int out_w32, int n, uint32_t* __restrict__ table, int wbits,   // out may be base (pai_ct_mul in place)
                  const MontCtx* __restrict__ fin) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int t = G::gl();

@@ -405,7 +405,7 @@ PAI_DEV uint32_t lds_limb(const uint4* A, const uint4* B, int J) {
 template <int NL, int U, bool OBF, bool GFORM>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_encrypt_padic(EncPadicParams P, const uint32_t* __restrict__ m, const uint32_t* __restrict__ r,
-                const uint32_t* __restrict__ ct_in, uint32_t* __restrict__ ct_out, int n, int mode) {
+                const uint32_t* ct_in, uint32_t* ct_out, int n, int mode) {            // ct_out is ct_in under pai_obfuscate
     using E = Padic<NL, U, false>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     // the modulus and n - 1 are read from LDS (broadcast reads): through the kernel-argument struct the
@@ -604,7 +604,7 @@ struct CtMulPadicParams {
 // multiply by the table's entry 0 (= 1).  Squarings run as products (see kernels_padic.hpp on the 72-limb squaring).
 template <int NL, int U>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
-k_ctmul_padic(CtMulPadicParams P, const uint32_t* __restrict__ ct, const uint32_t* __restrict__ e, uint32_t* __restrict__ out, int n) {
+k_ctmul_padic(CtMulPadicParams P, const uint32_t* ct, const uint32_t* __restrict__ e, uint32_t* out, int n) {     // out may be ct (pai_ct_mul in place)
     using E = Padic<NL, U, false>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* ldsn = lds + (BLOCK_THREADS / 64) * 2 * E::DIGIT_WORDS;

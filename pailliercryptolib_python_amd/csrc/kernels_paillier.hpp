@@ -65,8 +65,8 @@ struct EncParams {
 // mode 4: ct = ct_in * obf
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, PAI_LG_WAVES(G))
-k_encrypt(EncParams P, const uint32_t* __restrict__ m, const uint32_t* __restrict__ r,
-          const uint32_t* __restrict__ ct_in, uint32_t* __restrict__ ct_out, int n, int mode) {
+k_encrypt(EncParams P, const uint32_t* __restrict__ m, const uint32_t* r,
+          const uint32_t* ct_in, uint32_t* ct_out, int n, int mode) {      // ct_out may be ct_in (pai_obfuscate) or r (pai_ct_add_plain in place)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     typename G::NM nm;
     load_modulus<G>(nm, P.nsq, lds);
@@ -143,7 +143,7 @@ k_encrypt(EncParams P, const uint32_t* __restrict__ m, const uint32_t* __restric
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, PAI_LG_WAVES(G))
 k_encrypt_tree(EncParams P, const uint32_t* __restrict__ m, const uint32_t* __restrict__ r,
-               const uint32_t* __restrict__ ct_in, uint32_t* __restrict__ ct_out, int n, int mode) {
+               const uint32_t* ct_in, uint32_t* ct_out, int n, int mode) {             // ct_out is ct_in under pai_obfuscate
     static_assert(G::T >= 16 && G::T <= 64 && BLOCK_THREADS == 256, "one to four integers per wave, four waves");
     constexpr int EPW = 64 / G::T;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -273,8 +273,8 @@ k_fb_to_m1(const MontCtx* __restrict__ ctx, const uint32_t* __restrict__ in, uin
 // A kernel of its own: as extra modes of k_encrypt it cost that kernel's fixed-base loop 50 % (36x8: 61 -> 94 ms per 65536).
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, 2)
-k_pair_finish(EncParams P, const uint32_t* __restrict__ wv, int wv_words, const uint32_t* __restrict__ ct_in,
-              uint32_t* __restrict__ ct_out, int n, int mul_ct) {
+k_pair_finish(EncParams P, const uint32_t* __restrict__ wv, int wv_words, const uint32_t* ct_in,
+              uint32_t* ct_out, int n, int mul_ct) {                                   // ct_out is ct_in under pai_obfuscate
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     typename G::NM nm;
     load_modulus<G>(nm, P.nsq, lds);
@@ -648,8 +648,8 @@ k_dec_a_rl(DecAParams P, const uint32_t* __restrict__ ct, uint32_t* __restrict__
 // fin: M's own context (as k_modexp_var_win on these geometries).
 template <class G>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
-k_modexp_rl(const MontCtx* __restrict__ ctx, const uint32_t* __restrict__ base, int base_w32, const uint32_t* __restrict__ expo,
-            int ew, int ebits_max, int exp_bcast, uint32_t* __restrict__ out, int out_w32, int n, const MontCtx* __restrict__ fin) {
+k_modexp_rl(const MontCtx* __restrict__ ctx, const uint32_t* base, int base_w32, const uint32_t* __restrict__ expo,
+            int ew, int ebits_max, int exp_bcast, uint32_t* out, int out_w32, int n, const MontCtx* __restrict__ fin) {   // out may be base (pai_ct_mul in place)
     static_assert(G::M1 && G::EPB >= 2 && BLOCK_THREADS == 256, "minus-one geometries, two wave pairs per workgroup");
     constexpr int HALF = G::EPB / 2;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];

@@ -77,6 +77,24 @@ void require(bool ok, const char* msg) {
     if (!ok) throw PaiError(PAI_E_INVALID, msg);
 }
 
+// The aliasing rule of the ABI (include/paillier_hip.h, "memory contract"): an output range may be exactly an operand's range
+// where the call says so (same_ok); any other overlap of the two byte ranges is PAI_E_INVALID, before anything is launched.
+void require_no_overlap(const void* out, size_t out_bytes, const void* op, size_t op_bytes, bool same_ok, const char* msg) {
+    const uintptr_t o = reinterpret_cast<uintptr_t>(out), p = reinterpret_cast<uintptr_t>(op);
+    if (!out || !op || !out_bytes || !op_bytes) return;
+    if (same_ok && o == p && out_bytes == op_bytes) return;
+    if (o < p + op_bytes && p < o + out_bytes) throw PaiError(PAI_E_INVALID, msg);
+}
+
+// d_out of an element-wise a (x) b over N rows of `words` words: exactly d_a or exactly d_b, or apart from both.  A broadcast row
+// inside a longer output is refused: other waves still load it while row 0 of the output is stored.
+void require_out_ab(const uint32_t* d_a, const uint32_t* d_b, int b_bcast, size_t N, const uint32_t* d_out, int words) {
+    const size_t row = (size_t)words * 4, all = N * row;
+    require_no_overlap(d_out, all, d_a, all, true, "d_out overlaps d_a (an output may be exactly an operand, nothing else)");
+    require_no_overlap(d_out, all, d_b, b_bcast ? row : all, true,
+                       b_bcast ? "d_out overlaps the broadcast row d_b" : "d_out overlaps d_b (an output may be exactly an operand, nothing else)");
+}
+
 int words_for_bits(int bits) { return (bits + 31) / 32; }
 
 struct DeviceInfo {
@@ -833,9 +851,10 @@ int pai_buf_slice(int device, const uint32_t* d_src, int row_words, size_t start
     return guarded([&] {
         require(d_src && d_out && row_words > 0 && step >= 1, "bad arguments");
         if (count == 0) return;
-        DeviceScope scope_(device);
         const size_t row_bytes = (size_t)row_words * 4;
         const uint32_t* src = d_src + start * (size_t)row_words;
+        require_no_overlap(d_out, count * row_bytes, src, ((count - 1) * step + 1) * row_bytes, false, "pai_buf_slice: d_out overlaps the rows it reads");
+        DeviceScope scope_(device);
         if (step == 1) {
             HIP_CHECK(hipMemcpyAsync(d_out, src, count * row_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         } else {
@@ -847,8 +866,9 @@ int pai_buf_slice(int device, const uint32_t* d_src, int row_words, size_t start
 // out[i] = src[(i + shift) mod N]   (std::rotate to the left by `shift`, as CipherText::rotate)
 int pai_buf_rotate(int device, const uint32_t* d_src, int row_words, size_t N, long long shift, uint32_t* d_out, void* stream) {
     return guarded([&] {
-        require(d_src && d_out && row_words > 0 && d_src != d_out, "bad arguments");
+        require(d_src && d_out && row_words > 0, "bad arguments");
         if (N == 0) return;
+        require_no_overlap(d_out, N * (size_t)row_words * 4, d_src, N * (size_t)row_words * 4, false, "pai_buf_rotate: d_out overlaps d_src");
         DeviceScope scope_(device);
         const long long n = (long long)N;
         const size_t k = (size_t)(((shift % n) + n) % n);
@@ -961,6 +981,7 @@ int pai_modmul(pai_modulus* m, const uint32_t* d_a, const uint32_t* d_b, int b_b
     return guarded([&] {
         require(m && d_a && d_b && d_out, "NULL argument");
         if (N == 0) return;
+        require_out_ab(d_a, d_b, b_bcast, N, d_out, m->ms.w32);
         DeviceScope scope_(m->device);
         const GeoOps* g = m->ms.geo;
         g->modmul((hipStream_t)stream, grid_for(g, N, m->dev.ncu), m->ms.d_ctx, d_a, d_b, d_out, (int)N, m->ms.w32, b_bcast, MODMUL_FULL, nullptr);
