@@ -40,6 +40,7 @@ PROTOTYPES = {
     "pai_profile_enable": (C.c_int, [C.c_int]),
     "pai_profile_last": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_float)]),
     "pai_profile_last_path": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
+    "pai_profile_last_mode": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
     "pai_malloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(voidp)]),
     "pai_free": (C.c_int, [C.c_int, voidp]),
     "pai_memcpy_h2d": (C.c_int, [C.c_int, voidp, voidp, C.c_size_t, voidp]),

@@ -22,6 +22,7 @@ struct DecPadicParams {
     int sqr_kara;                // 36-limb primes: squarings by sqr_kara (MODE PADIC_LDS_K) instead of the row-wise sqr
     int mul_kara;                // ... and the products too, digits kept in registers between operations (MODE PADIC_LDS_KM)
     int red_kara;                // ... and the quotient products of the reductions (MODE PADIC_LDS_KMR); needs mul_kara
+    int bal_kara;                // ... on balanced digits, one carry stream per column (MODE PADIC_LDS_KMRB); needs red_kara
 };
 
 // (A, B) <- Montgomery digit form of the packed integer `row` (row_words 32-bit words, any value < s^2 R-ish):
@@ -108,7 +109,12 @@ constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 //                   (mont_padic.hpp: kara_pass<FORM, true>) in both passes of a squaring and the first pass of a product, and the
 //                   product streams of those three passes as one chain per column (PADIC_KMR_RED; which passes: measured,
 //                   profiles/r14/README.md).  Same kernel body, same LDS, same table.
-constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4;
+// MODE PADIC_LDS_KMRB: PADIC_LDS_KMR on balanced digits (mont_padic.hpp: kara_pass_bal): limbs in [-2^28, 2^28) from the end of
+//                   the digit-form entry to the exit product, so that a whole column (product and quotient products) fits ONE
+//                   signed 64-bit cell — one carry stream, one shift and one digit extraction per column, no 128-bit cell.
+//                   The table holds the balanced limbs as they are (same format and size); the row-wise entry and exit are
+//                   those of the other modes, with one carry pass per digit on either side.
+constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4, PADIC_LDS_KMRB = 5;
 constexpr bool padic_reg_mode(int mode) { return mode == PADIC_LDS_KM || mode == PADIC_LDS_KMR; }
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
@@ -169,7 +175,62 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         const uint32_t* row = ct + (size_t)es * P.ct_words;
         // ---- digit form of ct:  sum_i  (c_i, 0) * digits(R^(i+2) mod s^2) -----------------------------
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
-        if constexpr (padic_reg_mode(MODE)) {
+        if constexpr (MODE == PADIC_LDS_KMRB) {
+            // ---- the loop of PADIC_LDS_KM / PADIC_LDS_KMR below (same steps, same table slots) on balanced digits --------
+            const int NT = P.tbl_entries;
+            int32_t nb[NL];                               // balanced modulus limbs: wave-uniform, formed once from the SGPR copy
+            E::to_balanced(sn, nb);
+            int32_t a[NL], b[NL];
+            {
+                uint32_t ua[NL], ub[NL];
+                E::load_digit(A, ua);
+                E::load_digit(B, ub);
+                E::to_balanced(ua, a);
+                E::to_balanced(ub, b);
+            }
+            auto put = [&](int e) {
+#pragma unroll
+                for (int c = 0; c < E::NC; ++c) {
+                    tbl(e, 0, c) = make_uint4((uint32_t)a[4 * c], (uint32_t)a[4 * c + 1], (uint32_t)a[4 * c + 2], (uint32_t)a[4 * c + 3]);
+                    tbl(e, 1, c) = make_uint4((uint32_t)b[4 * c], (uint32_t)b[4 * c + 1], (uint32_t)b[4 * c + 2], (uint32_t)b[4 * c + 3]);
+                }
+            };
+            put(0);
+            const int i0 = (int)(ops[0] >> 8);
+            const int steps = NT + nops - 1;
+#pragma unroll 1
+            for (int t = 0; t < steps; ++t) {
+                int nsq = 0, idx = NT, put_e = t, get_e = -1;
+                if (t == 0) { nsq = 1; idx = 0xFF; put_e = NT; get_e = 0; }
+                else if (t >= NT) {
+                    const int op = (int)ops[t - NT + 1];
+                    nsq = op & 0xFF; idx = op >> 8; put_e = -1;
+                }
+                if (t == NT - 1) get_e = i0;
+#pragma unroll 1
+                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<E::PADIC_KMRB_RED>(a, b, nb, n0inv);
+                if (idx != 0xFF)
+                    E::template mul_kara_reg_bal<E::PADIC_KMRB_RED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
+                if (put_e >= 0) put(put_e);
+                if (get_e >= 0) {
+#pragma unroll
+                    for (int c = 0; c < E::NC; ++c) {
+                        const uint4 ta = tbl(get_e, 0, c), tb = tbl(get_e, 1, c);
+                        a[4 * c] = (int32_t)ta.x; a[4 * c + 1] = (int32_t)ta.y; a[4 * c + 2] = (int32_t)ta.z; a[4 * c + 3] = (int32_t)ta.w;
+                        b[4 * c] = (int32_t)tb.x; b[4 * c + 1] = (int32_t)tb.y; b[4 * c + 2] = (int32_t)tb.z; b[4 * c + 3] = (int32_t)tb.w;
+                    }
+                }
+            }
+            // back to a pair the row-wise exit takes, the same residue modulo s^2:  a + b s = (a + s) + (b - 1 + s) s - s^2,
+            // both in (0.49 s - 1, 1.51 s) (2.01 s where the schedule is empty and the entry's pair comes straight back)
+            uint32_t ua[NL], ub[NL];
+            E::from_balanced_plus_p(a, nb, 0, ua);
+            E::from_balanced_plus_p(b, nb, 1, ub);
+            wave_lds_fence();
+            E::store_digit(A, ua);
+            E::store_digit(B, ub);
+            wave_lds_fence();
+        } else if constexpr (padic_reg_mode(MODE)) {
             constexpr int RED = MODE == PADIC_LDS_KMR ? E::PADIC_KMR_RED : 0;
             // ---- table of odd powers and sliding-window schedule on register digits ----------------------------------
             // ONE loop and so one inlined copy of the squaring and of the product (each is tens of KB of straight-line

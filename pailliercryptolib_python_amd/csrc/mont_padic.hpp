@@ -983,6 +983,260 @@ struct Padic {
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }
 
+    // ---- the same on BALANCED digits: one carry stream per column (kernels_padic.hpp: PADIC_LDS_KMRB) -------------------------
+    // Every limb is a signed digit in [-2^28, 2^28) (int32; the top limb holds whatever small signed carry is left), the
+    // modulus limbs nm likewise, and so are the quotient digits: m == -x y / p (mod R) with digits in [-2^28, 2^28), i.e.
+    // |m| <= (2^28 / (2^29 - 1)) R < R/2 (1 + 2^-28).  The product rule loses its offsets:
+    //        w = (a c + m p) / R,        v = (a d + b c - m + m' p) / R
+    // and w + v p == (a + b p)(c + d p) R^-1 (mod p^2) as before (a c = R w - m p, R v = a d + b c - m + m' p).
+    // Cells.  A limb product is at most 2^56 in magnitude, so with NL <= 36 the finished column
+    //        d_k = [2] X_k  - min_k  + sum_i mq_i nm_(k-i)  + carry        (X_k: NL products, or 2 NL for a d + b c)
+    // is below 36 (2^57 + 2^56) + 2^28 + 2^35 < 2^62.76 in magnitude for all four FORMs and lies inside ONE signed 64-bit
+    // cell: there is no second stream (cc), no low-bits hand-over and no 128-bit middle cell.  Every stored sum (V_k, U_k,
+    // P0 / P2, -D, -E) and every partial sum need only be exact modulo 2^64; only the finished d_k is shifted, arithmetically.
+    // Differences of balanced digits are below 2^29, D_j and E_j below 18 2^58 in magnitude as in the unsigned form.
+    // Digits.  k < NL: mq_k = the signed 29-bit field of d_k n0inv, then d_k + mq_k nm_0 == 0 (mod 2^29) and the carry
+    // d_k >> 29 is exact.  k >= NL: out_(k-NL) = the signed 29-bit field of d_k and the carry is (d_k + 2^28) >> 29; the last
+    // carry is the top limb.  |carry| <= 2^62.76 / 2^29 + 1 < 2^34.
+    // Invariant.  For |a|, |b|, |c|, |d| < 0.51 p and R / p >= 2^20:  |w| <= (0.2601 p^2 + |m| p) / R < (0.2601 2^-20 + 0.5
+    // (1 + 2^-28)) p < 0.51 p, and |v| <= (0.5202 p^2 + |m| + |m'| p) / R < (0.5202 2^-20 + 0.5 (1 + 2^-28)) p + 0.51 < 0.51 p.
+    // (Operands up to 2.01 p, the digit-form entry's lazy range, give |w|, |v| < (8.1 2^-20 + 0.5 (1 + 2^-28)) p + 0.51 as well.)
+    // The Karatsuba identities of kara_pass (X_k, KRED: Y_k = U_k + U_(k-H) - E_(k-H), VF: X_k = V_k + V_(k-H) - D_(k-H)) are
+    // identities over the integers and hold for signed limbs unchanged.  VF here serves all four FORMs: the sum of two
+    // products is one chain V_k as well.  Cells: tools/kara_model.py (kara_pass_bal).
+    PAI_DEV static int32_t sfield(uint32_t v) { return (int32_t)(v << (32 - RB)) >> (32 - RB); }
+    PAI_DEV static uint64_t smul(int32_t a, int32_t b) { return (uint64_t)((int64_t)a * (int64_t)b); }
+    template <int FORM, bool KRED = false, bool VF = false>
+    PAI_DEV static void kara_pass_bal(int32_t (&out)[NL], int32_t (&mq)[NL], const int32_t (&x)[NL], const int32_t (&y)[NL],
+                                      const int32_t (&x2)[NL], const int32_t (&y2)[NL], const int32_t (&min)[NL],
+                                      const int32_t* __restrict__ nm, uint32_t n0inv) {
+        static_assert(NL % 2 == 0 && NL <= 36, "even limb count; NL (2^57 + 2^56) < 2^63");
+        constexpr bool SYM = FORM == KARA_SQR, DBL = FORM == KARA_SQR2, SUM = FORM == KARA_MUL2;
+        constexpr bool SECOND = DBL || SUM;               // - min enters the reduction columns
+        constexpr int H = NL / 2, NP = 2 * H - 1;
+        int32_t nx[H], dy[H], nx2[H], dy2[H];             // as in kara_pass; SYM without VF: dy2 = dy doubled
+        int32_t yd[NL];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            nx[i] = x[i + H] - x[i];
+            dy[i] = y[i] - y[i + H];
+            nx2[i] = SUM ? x2[i + H] - x2[i] : 0;
+            dy2[i] = SUM ? y2[i] - y2[i + H] : dy[i] * 2;
+        }
+#pragma unroll
+        for (int i = 0; i < NL; ++i) yd[i] = y[i] * 2;
+        auto half = [&](int o, int j) -> uint64_t {
+            uint64_t s = 0;
+            const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+            for (int i = lo; i <= hi; ++i) {
+                const int l = j - i;
+                if (!SYM) s += smul(x[o + i], y[o + l]);
+                else if (i < l) s += smul(x[o + i], yd[o + l]);
+                else if (i == l) s += smul(x[o + i], y[o + i]);
+                if (SUM) s += smul(x2[o + i], y2[o + l]);
+            }
+            return s;
+        };
+        uint64_t p0[NP], p2[NP];
+        uint64_t pv[H + NP];
+        uint64_t ru[H + NP];
+        int32_t dm[H], ndp[H];
+        if constexpr (KRED) {
+#pragma unroll
+            for (int l = 0; l < H; ++l) ndp[l] = nm[H + l] - nm[l];
+        }
+        // -1 as a run-time scalar (n0inv is odd): - min[k] then is ONE signed multiply-add onto the column; with the literal
+        // the compiler emits sign extension, subtract and borrow (three instructions, 36 columns)
+        const int32_t neg1 = -(int32_t)(n0inv & 1u);
+        uint64_t carry = 0;
+#pragma unroll
+        for (int k = 0; k < 2 * NL - 1; ++k) {
+            uint64_t t = 0;                               // the product column X_k, exact modulo 2^64
+            if constexpr (VF) {
+                const bool mid = k >= H && k - H < NP;
+                uint64_t vk = 0, off = 0, nd = 0;
+                if (k < NP) {
+                    const int lo = k < H ? 0 : k - H + 1, hi = k < H ? k : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = k - i;
+                        if (!SYM) vk += smul(x[i], y[l]);
+                        else if (i < l) off += smul(x[i], y[l]);
+                        else if (i == l) vk += smul(x[i], y[i]);
+                        if (SUM) vk += smul(x2[i], y2[l]);
+                    }
+                }
+                if (mid) {
+                    const int j = k - H;
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (!SYM) vk += smul(x[H + i], y[H + l]);
+                        else if (i < l) off += smul(x[H + i], y[H + l]);
+                        else if (i == l) vk += smul(x[H + i], y[H + i]);
+                        if (SUM) vk += smul(x2[H + i], y2[H + l]);
+                    }
+                }
+                if (SYM) vk += off << 1;
+                if (k < H + NP) pv[k] = vk;
+                t = vk;
+                if (k >= H) t += pv[k - H];
+                if (mid) {
+                    const int j = k - H;
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (!SYM) t += smul(nx[i], dy[l]);
+                        else if (i < l) nd += smul(nx[i], dy[l]);
+                        else if (i == l) t += smul(nx[i], dy[i]);
+                        if (SUM) t += smul(nx2[i], dy2[l]);
+                    }
+                    if (SYM) t += nd << 1;
+                }
+            } else {
+                if (k < NP) { p0[k] = half(0, k); t += p0[k]; }
+                if (k >= H && k - H < NP) {
+                    const int j = k - H;
+                    p2[j] = half(H, j);
+                    t += p0[j] + p2[j];
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (!SYM) t += smul(nx[i], dy[l]);
+                        else if (i < l) t += smul(nx[i], dy2[l]);
+                        else if (i == l) t += smul(nx[i], dy[i]);
+                        if (SUM) t += smul(nx2[i], dy2[l]);
+                    }
+                }
+                if (k >= 2 * H) t += p2[k - 2 * H];
+            }
+            uint64_t d = DBL ? t << 1 : t;
+            if (SECOND && k < NL) d += smul(min[k], neg1);
+            if constexpr (KRED) {
+                constexpr int NU = H + NP;
+                const bool has_u = k < NU, mid = k >= H && k - H < NP;
+                uint64_t u = 0;
+                if (k < NP) {
+                    const int lo0 = k < H ? 0 : k - H + 1, hi0 = k < H ? k - 1 : H - 1;
+#pragma unroll
+                    for (int i = lo0; i <= hi0; ++i)
+                        if (i != k - 1) u += smul(mq[i], nm[k - i]);
+                }
+                if (mid) {
+                    const int j = k - H;
+                    const int lo2 = j < H ? 0 : j - H + 1, hi2 = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo2; i <= hi2; ++i) {
+                        const int l = j - i;
+                        if (i == j && k < NL) {
+                            d += smul(mq[i], ndp[0]);
+                        } else if (H + i != k - 1) {
+                            u += smul(mq[H + i], nm[H + l]);
+                            d += smul(dm[i], ndp[l]);
+                        }
+                    }
+                }
+                if (k >= H) d += ru[k - H];
+                d += carry;
+                if (k >= 1 && k <= H) u += smul(mq[k - 1], nm[1]);
+                if (k - 1 >= H && k - 1 < NL) {
+                    u += smul(mq[k - 1], nm[H + 1]);
+                    d += smul(dm[k - 1 - H], ndp[1]);
+                }
+                if (k < H) {
+                    mq[k] = sfield(((uint32_t)d + (uint32_t)u) * n0inv);
+                    u += smul(mq[k], nm[0]);
+                    d += u;
+                } else {
+                    if (has_u) d += u;
+                    if (k < NL) {
+                        mq[k] = sfield((uint32_t)d * n0inv);
+                        d += smul(mq[k], nm[0]);
+                        u += smul(mq[k], nm[H]);
+                        dm[k - H] = mq[k - H] - mq[k];
+                    } else {
+                        out[k - NL] = sfield((uint32_t)d);
+                    }
+                }
+                if (has_u) ru[k] = u;
+            } else {
+                const int lo = k < NL ? 0 : k - NL + 1, hi = k < NL ? k - 1 : NL - 1;
+#pragma unroll
+                for (int i = lo; i <= hi; ++i)
+                    if (i != k - 1) d += smul(mq[i], nm[k - i]);
+                d += carry;
+                if (k >= 1 && k - 1 < NL) d += smul(mq[k - 1], nm[1]);
+                if (k < NL) {
+                    mq[k] = sfield((uint32_t)d * n0inv);
+                    d += smul(mq[k], nm[0]);
+                } else {
+                    out[k - NL] = sfield((uint32_t)d);
+                }
+            }
+            carry = (uint64_t)((int64_t)(k < NL ? d : d + (1ull << (RB - 1))) >> RB);
+        }
+        out[NL - 1] = (int32_t)carry;
+    }
+    // RED as for sqr_kara_reg / mul_kara_reg; KRED_VFS = the sum of two products (second pass of a product) as one chain V_k
+    // too, which the single cell makes possible: 449.8 -> 444.3 ms per step against the summed half products; that pass's
+    // reduction by U_k on top was not faster in the unsigned form (profiles/r14/) and costs registers here (profiles/r15/)
+    static constexpr int KRED_VFS = 64;
+    static constexpr int PADIC_KMRB_RED = PADIC_KMR_RED | KRED_VFS;
+    template <int RED = 0>
+    PAI_DEV static void sqr_kara_reg_bal(int32_t (&a)[NL], int32_t (&b)[NL], const int32_t* __restrict__ nm, uint32_t n0inv) {
+        constexpr bool VF = (RED & KRED_VF) != 0;
+        int32_t m[NL], w[NL], m2[NL], v[NL];
+        kara_pass_bal<KARA_SQR, kred(RED, KARA_SQR), VF>(w, m, a, a, a, a, m, nm, n0inv);
+        kara_pass_bal<KARA_SQR2, kred(RED, KARA_SQR2), VF>(v, m2, a, b, a, b, m, nm, n0inv);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
+    }
+    template <int RED = 0, class RSrc>
+    PAI_DEV static void mul_kara_reg_bal(int32_t (&a)[NL], int32_t (&b)[NL], RSrc&& rsrc, const int32_t* __restrict__ nm,
+                                         uint32_t n0inv) {
+        int32_t c[NL], d[NL], m[NL], w[NL], m2[NL], v[NL];
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            const uint4 t = rsrc(0, ch);
+            c[4 * ch] = (int32_t)t.x; c[4 * ch + 1] = (int32_t)t.y; c[4 * ch + 2] = (int32_t)t.z; c[4 * ch + 3] = (int32_t)t.w;
+        }
+        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0>(w, m, a, c, a, c, m, nm, n0inv);
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            const uint4 t = rsrc(1, ch);
+            d[4 * ch] = (int32_t)t.x; d[4 * ch + 1] = (int32_t)t.y; d[4 * ch + 2] = (int32_t)t.z; d[4 * ch + 3] = (int32_t)t.w;
+        }
+        kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0>(v, m2, a, d, b, c, m, nm, n0inv);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
+    }
+    // lazy unsigned limbs (value < R / 2) -> balanced digits of the same integer; the top limb keeps the rest
+    PAI_DEV static void to_balanced(const uint32_t (&x)[NL], int32_t (&r)[NL]) {
+        int32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < NL - 1; ++j) {
+            const int32_t t = (int32_t)x[j] + c;
+            r[j] = sfield((uint32_t)t);
+            c = (t + (1 << (RB - 1))) >> RB;
+        }
+        r[NL - 1] = (int32_t)x[NL - 1] + c;
+    }
+    // balanced digits of x, |x| < R / 4, plus the balanced modulus (less `less`: 0 or 1) -> limbs in [0, 2^29) of x + p - less
+    // (> 0 for |x| < 0.51 p)
+    PAI_DEV static void from_balanced_plus_p(const int32_t (&x)[NL], const int32_t* __restrict__ nm, int32_t less, uint32_t (&r)[NL]) {
+        int32_t c = -less;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            const int32_t t = x[j] + nm[j] + c;
+            r[j] = (uint32_t)t & RMASK;
+            c = t >> RB;
+        }
+    }
+
     // (A, B) <- (A, B) * (C, D), the second operand's digits supplied per row block
     template <class CSrc, class DSrc>
     PAI_DEV static void mul(uint4* A, uint4* B, MBuf M, CSrc&& csrc, DSrc&& dsrc, const uint32_t* __restrict__ nm,

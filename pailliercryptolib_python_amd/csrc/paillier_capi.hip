@@ -364,13 +364,14 @@ static MsbCtx* build_msb_ctx(const Limbs& M, const GeoOps* g, int w32) {
 // bench.py to report the dominant kernel's duration next to the rocprofv3 numbers.  `path` names the kernel family the dispatcher
 // chose where one name covers several (pai_profile_last_path: the tests' proof that a forced family ran).
 bool g_profile = false;
-struct KernelTime { std::string name; float ms; const char* path; };
+struct KernelTime { std::string name; float ms; const char* path; const char* mode; };
 thread_local std::vector<KernelTime> g_last_times;
 struct ScopedKernelTimer {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipStream_t s;
     const char* name;
     const char* path;
+    const char* mode = "";           // the kernel within the family where several share a path (pai_profile_last_mode)
     bool on;
     ScopedKernelTimer(const char* n, hipStream_t st, const char* p = "") : s(st), name(n), path(p), on(g_profile) {
         if (!on) return;
@@ -384,7 +385,7 @@ struct ScopedKernelTimer {
         HIP_CHECK(hipEventSynchronize(e1));
         float ms = 0.f;
         HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        g_last_times.push_back({name, ms, path});
+        g_last_times.push_back({name, ms, path, mode});
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         e0 = e1 = nullptr;
@@ -403,6 +404,8 @@ struct ScopedKernelTimer {
 //                                  serve), pair, pair_ctmul, wide, gform (plain fixed-base tables), fb_chain, lat_dense, lat_enc_m1, lat_add_m1
 //                                  padic_kara (36-limb decrypt squarings row-wise instead of by Karatsuba columns),
 //                                  padic_kara_red (36-limb decrypt: quotient products of the Montgomery reductions schoolbook, kernel mode PADIC_LDS_KM),
+//                                  padic_balanced (36-limb decrypt: unsigned limbs with two carry streams per column, kernel mode PADIC_LDS_KMR,
+//                                  instead of balanced digits, PADIC_LDS_KMRB),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch),
 //                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key)
@@ -808,6 +811,12 @@ int pai_profile_last(int index, char* name_out, size_t name_cap, float* ms_out) 
         name_out[name_cap - 1] = 0;
     }
     if (ms_out) *ms_out = g_last_times[index].ms;
+    return PAI_OK;
+}
+int pai_profile_last_mode(int index, char* mode_out, size_t mode_cap) {
+    if (index < 0 || (size_t)index >= g_last_times.size() || !mode_out || !mode_cap) return PAI_E_INVALID;
+    std::strncpy(mode_out, g_last_times[index].mode, mode_cap - 1);
+    mode_out[mode_cap - 1] = 0;
     return PAI_OK;
 }
 int pai_profile_last_path(int index, char* path_out, size_t path_cap) {

@@ -18,6 +18,7 @@ value and records the largest one, and it asserts that
     products in -D): the chains, the doubled sums and V_k fit 64 bits resp. int64, X_k is the schoolbook column,
   - for a product: the summed half products of a d + b c fit 64 bits, their signed difference part fits int64, the middle
     part is non-negative and enters through a 128-bit cell, and w, v are those of the row-wise product rule.
+The balanced-digit form (kara_pass_bal, one signed 64-bit cell per column) has its own model below: kara_pass_bal.
 Run: python tools/kara_model.py [rounds]
 """
 import random
@@ -342,6 +343,361 @@ def sqr_kara(a, b, p, NL, st, in_range=True, red=0):
     return W, V
 
 
+# ---- balanced digits: one carry stream per column (kara_pass_bal, sqr_kara_reg_bal, mul_kara_reg_bal; kernel mode
+# PADIC_LDS_KMRB) ---------------------------------------------------------------------------------------------------------
+# Limbs are signed digits in [-2^28, 2^28) (the top limb keeps what is left), the modulus limbs and the quotient digits
+# too.  The model follows kara_pass_bal cell by cell on unbounded integers and asserts that
+#   - every limb, difference limb and quotient digit fits int32 and every signed product int64,
+#   - every stored sum is within its bound: |V_k| <= H 2^56 (2 H 2^56 for the sum of two products), |U_k| <= H 2^56, the half
+#     products likewise, |D_j|, |E_j| partial sums < H 2^58 — so each 64-bit cell holds its value exactly, not only modulo 2^64,
+#   - the finished column d_k is the schoolbook column [2] X_k - min_k + sum_i mq_i nm_(k-i) + carry and |d_k| < 2^63,
+#   - mq and out (all but the top limb) are in [-2^28, 2^28), d_k + mq_k nm_0 == 0 (mod 2^29) for k < NL,
+#   - (callers) w R = x y + m p and v R = a d + b c - m + m' p exactly.
+VFS = 64                              # mul_kara_reg_bal<RED>: the second pass of a product (sum of two products) as one chain too
+KMRB_RED = KMR_RED | VFS              # Padic::PADIC_KMRB_RED: what kernel mode PADIC_LDS_KMRB runs
+HB = B >> 1                           # 2^28
+
+
+def sfield(v):
+    """The signed 29-bit field of a word."""
+    v &= MASK
+    return v - B if v >= HB else v
+
+
+def bal_limbs(x, n):
+    """Balanced digits of the signed integer x: n - 1 digits in [-2^28, 2^28), the top limb keeps the rest."""
+    out = []
+    for _ in range(n - 1):
+        r = sfield(x)
+        out.append(r)
+        x = (x - r) >> RB
+    out.append(x)
+    return out
+
+
+def to_balanced(x):
+    """Padic::to_balanced: lazy unsigned limbs -> balanced digits of the same integer (int32 cells)."""
+    r, c = [], 0
+    for j in range(len(x) - 1):
+        t = x[j] + c
+        assert -(1 << 31) <= t + HB < (1 << 31)
+        r.append(sfield(t))
+        c = (t + HB) >> RB
+    r.append(x[-1] + c)
+    assert -(1 << 31) <= r[-1] < (1 << 31)
+    return r
+
+
+def from_balanced_plus_p(x, nb, less):
+    """Padic::from_balanced_plus_p: balanced digits of x and of p -> limbs in [0, 2^29) of x + p - less (which must lie in [0, R))."""
+    r, c = [], -less
+    for j in range(len(x)):
+        t = x[j] + nb[j] + c
+        assert -(1 << 31) <= t < (1 << 31)
+        r.append(t & MASK)
+        c = t >> RB
+    assert c == 0, "x + p - less leaves [0, R)"
+    return r
+
+
+class BalStats:
+    def __init__(self):
+        self.max_d = self.max_v = self.max_u = self.max_e = 0
+        self.red_macs = 0
+
+
+def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False):
+    """One pass of kara_pass_bal<FORM, KRED, VF> on signed limb lists; returns (out limbs, quotient limbs)."""
+    form = int(form)
+    sym, dbl, summ = form == SQR, form == SQR2, form == MUL2
+    second = dbl or summ
+    NL = len(x)
+    H = NL // 2
+    NP = 2 * H - 1
+    assert NL % 2 == 0 and NL <= 36
+    i32 = lambda v: -(1 << 31) <= v < (1 << 31)
+    for v in list(x) + list(y) + list(x2 or []) + list(y2 or []) + list(mnin) + list(nm):
+        assert i32(v)
+    nx = [x[i + H] - x[i] for i in range(H)]
+    dy = [y[i] - y[i + H] for i in range(H)]
+    nx2 = [x2[i + H] - x2[i] for i in range(H)] if summ else [0] * H
+    dy2 = [y2[i] - y2[i + H] for i in range(H)] if summ else [2 * d for d in dy]
+    yd = [2 * v for v in y]
+    ndp = [nm[H + l] - nm[l] for l in range(H)]
+    for v in nx + dy + nx2 + dy2 + yd + ndp:
+        assert i32(v), "difference or doubled limb leaves int32"
+    vbound = (2 if summ else 1) * H << 56
+    dbound = (2 if summ else 1) * H << 58
+
+    def smul(a, b):
+        assert i32(a) and i32(b)
+        pr = a * b
+        assert -(1 << 63) <= pr < (1 << 63)
+        return pr
+
+    def rng(j):
+        return (0, j) if j < H else (j - H + 1, H - 1)
+
+    def half(o, j):
+        s = 0
+        lo, hi = rng(j)
+        for i in range(lo, hi + 1):
+            l = j - i
+            if not sym:
+                s += smul(x[o + i], y[o + l])
+            elif i < l:
+                s += smul(x[o + i], yd[o + l])
+            elif i == l:
+                s += smul(x[o + i], y[o + i])
+            if summ:
+                s += smul(x2[o + i], y2[o + l])
+        assert abs(s) <= vbound, "half-product coefficient beyond its bound"
+        return s
+
+    def column(xx, yy, k):
+        return sum(xx[i] * yy[k - i] for i in range(max(0, k - NL + 1), min(k, NL - 1) + 1))
+
+    p0, p2 = [0] * NP, [0] * NP
+    pv = [0] * (H + NP)
+    ru = [0] * (H + NP)
+    dm = [0] * H
+    mq, out = [0] * NL, [0] * NL
+    carry = 0
+    macs = 0
+    for k in range(2 * NL - 1):
+        mid = H <= k < H + NP
+        t = 0
+        if vf:
+            vk = off = nd = 0
+            for o, jj, on in ((0, k, k < NP), (H, k - H, mid)):
+                if not on:
+                    continue
+                lo, hi = rng(jj)
+                for i in range(lo, hi + 1):
+                    l = jj - i
+                    if not sym:
+                        vk += smul(x[o + i], y[o + l])
+                    elif i < l:
+                        off += smul(x[o + i], y[o + l])
+                    elif i == l:
+                        vk += smul(x[o + i], y[o + i])
+                    if summ:
+                        vk += smul(x2[o + i], y2[o + l])
+            if sym:
+                vk += off << 1
+            assert abs(vk) <= vbound, "V_k beyond its bound"
+            st.max_v = max(st.max_v, abs(vk))
+            if k < H + NP:
+                pv[k] = vk
+            else:
+                assert vk == 0
+            t = vk + (pv[k - H] if k >= H else 0)
+            if mid:
+                j = k - H
+                lo, hi = rng(j)
+                e = 0
+                for i in range(lo, hi + 1):
+                    l = j - i
+                    if not sym:
+                        e += smul(nx[i], dy[l])
+                    elif i < l:
+                        nd += smul(nx[i], dy[l])
+                    elif i == l:
+                        e += smul(nx[i], dy[i])
+                    if summ:
+                        e += smul(nx2[i], dy2[l])
+                e += nd << 1
+                assert abs(e) < dbound, "-D_j beyond its bound"
+                t += e
+        else:
+            if k < NP:
+                p0[k] = half(0, k)
+                t += p0[k]
+            if mid:
+                j = k - H
+                p2[j] = half(H, j)
+                t += p0[j] + p2[j]
+                lo, hi = rng(j)
+                e = 0
+                for i in range(lo, hi + 1):
+                    l = j - i
+                    if not sym:
+                        e += smul(nx[i], dy[l])
+                    elif i < l:
+                        e += smul(nx[i], dy2[l])
+                    elif i == l:
+                        e += smul(nx[i], dy[i])
+                    if summ:
+                        e += smul(nx2[i], dy2[l])
+                assert abs(e) < dbound, "-D_j beyond its bound"
+                t += e
+            if k >= 2 * H:
+                t += p2[k - 2 * H]
+        want = column(x, y, k) + (column(x2, y2, k) if summ else 0)
+        assert t == want, (k, t, want)
+        d = (t << 1) if dbl else t
+        if second and k < NL:
+            d += smul(mnin[k], -1)
+        lo, hi = (0, k - 1) if k < NL else (k - NL + 1, NL - 1)
+        school = d + carry + sum(mq[i] * nm[k - i] for i in range(lo, hi + 1))
+        if not kred:
+            macs += hi - lo + 1 + (1 if k < NL else 0)
+            d = school
+            if k < NL:
+                mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+                d += smul(mq[k], nm[0])
+            else:
+                out[k - NL] = sfield(d)
+        else:
+            has_u, midr = k < H + NP, H <= k < H + NP
+            u = e = 0
+
+            def signed(a, b):
+                nonlocal d, e, macs
+                pr = smul(a, b)
+                e += pr
+                assert abs(e) < (H << 58), "partial sum of -E beyond its bound"
+                st.max_e = max(st.max_e, abs(e))
+                d += pr
+                macs += 1
+
+            if k < NP:
+                lo0, hi0 = (0, k - 1) if k < H else (k - H + 1, H - 1)
+                for i in range(lo0, hi0 + 1):
+                    if i != k - 1:
+                        u += smul(mq[i], nm[k - i])
+                        macs += 1
+            if midr:
+                j = k - H
+                lo2, hi2 = rng(j)
+                for i in range(lo2, hi2 + 1):
+                    l = j - i
+                    if i == j and k < NL:
+                        signed(mq[i], ndp[0])
+                    elif H + i != k - 1:
+                        u += smul(mq[H + i], nm[H + l])
+                        macs += 1
+                        signed(dm[i], ndp[l])
+            if k >= H:
+                d += ru[k - H]
+            d += carry
+            if 1 <= k <= H:
+                u += smul(mq[k - 1], nm[1])
+                macs += 1
+            if H <= k - 1 < NL:
+                u += smul(mq[k - 1], nm[H + 1])
+                macs += 1
+                signed(dm[k - 1 - H], ndp[1])
+            if k < H:
+                mq[k] = sfield(((((d & 0xFFFFFFFF) + (u & 0xFFFFFFFF)) & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+                u += smul(mq[k], nm[0])
+                macs += 1
+                d += u
+            else:
+                if has_u:
+                    d += u
+                if k < NL:
+                    assert d == school, (k, d, school)
+                    mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+                    d += smul(mq[k], nm[0])
+                    u += smul(mq[k], nm[H])
+                    macs += 2
+                    dm[k - H] = mq[k - H] - mq[k]
+                    assert i32(dm[k - H])
+                else:
+                    out[k - NL] = sfield(d)
+            assert abs(u) <= (H << 56), "U_k beyond its bound"
+            st.max_u = max(st.max_u, abs(u))
+            if has_u:
+                ru[k] = u
+            else:
+                assert u == 0
+        # the finished column: the schoolbook one, inside a signed 64-bit cell; only now it is shifted
+        assert d == school + (mq[k] * nm[0] if k < NL else 0), (k, d, school)
+        assert -(1 << 63) <= d and d + HB < (1 << 63), "finished column leaves int64"
+        st.max_d = max(st.max_d, abs(d))
+        if k < NL:
+            assert -HB <= mq[k] < HB and d % B == 0
+            carry = d >> RB
+        else:
+            assert -HB <= out[k - NL] < HB
+            carry = (d + HB) >> RB
+            assert carry * B + out[k - NL] == d
+    assert i32(carry)
+    out[NL - 1] = carry
+    st.red_macs = macs
+    return out, mq
+
+
+def _bal_ctx(p, NL):
+    return bal_limbs(p, NL), (-pow(p, -1, B)) % B
+
+
+def mul_kara_bal(al, bl, cl, dl, p, st, red=KMRB_RED):
+    """(a, b) * (c, d) -> (w, v) limb lists by mul_kara_reg_bal<red> on balanced limb lists; checks w R = a c + m p and
+    v R = a d + b c - m + m' p on the represented integers and the product rule modulo p^2."""
+    NL = len(al)
+    R = 1 << (RB * NL)
+    nm, n0inv = _bal_ctx(p, NL)
+    assert value(nm) == p
+    w, m = kara_pass_bal(MUL, al, cl, [0] * NL, nm, n0inv, st, kred=bool(red >> MUL & 1), vf=bool(red & VFM))
+    v, m2 = kara_pass_bal(MUL2, al, dl, m, nm, n0inv, st, x2=bl, y2=cl, kred=bool(red >> MUL2 & 1), vf=bool(red & VFS))
+    a, b, c, d = value(al), value(bl), value(cl), value(dl)
+    W, M, V, M2 = value(w), value(m), value(v), value(m2)
+    assert W * R == a * c + M * p
+    assert V * R == a * d + b * c - M + M2 * p
+    assert 2 * abs(M) <= R + (R >> 28) and 2 * abs(M2) <= R + (R >> 28)
+    p2 = p * p
+    assert (W + V * p - (a + b * p) * (c + d * p) * pow(R, -1, p2)) % p2 == 0
+    return w, v
+
+
+def sqr_kara_bal(al, bl, p, st, red=KMRB_RED):
+    """(a, b)^2 by sqr_kara_reg_bal<red> on balanced limb lists; checks w R = a^2 + m p and v R = 2 a b - m + m' p."""
+    NL = len(al)
+    R = 1 << (RB * NL)
+    nm, n0inv = _bal_ctx(p, NL)
+    w, m = kara_pass_bal(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF))
+    v, m2 = kara_pass_bal(SQR2, al, bl, m, nm, n0inv, st, kred=bool(red >> SQR2 & 1), vf=bool(red & VF))
+    a, b = value(al), value(bl)
+    W, M, V, M2 = value(w), value(m), value(v), value(m2)
+    assert W * R == a * a + M * p
+    assert V * R == 2 * a * b - M + M2 * p
+    p2 = p * p
+    assert (W + V * p - (a + b * p) ** 2 * pow(R, -1, p2)) % p2 == 0
+    return w, v
+
+
+def in_lazy_range(l, p):
+    """The invariant of the balanced engine: |value| < 0.51 p."""
+    return 100 * abs(value(l)) < 51 * p
+
+
+def run_bal(rounds=1, seed=2):
+    rng = random.Random(seed)
+    st = BalStats()
+    for bits, NL in ((1024, 36), (768, 36), (600, 24)):
+        H = NL // 2
+        for _ in range(rounds):
+            p = random_prime(bits, rng)
+            lo, hi = [-HB] * NL, [HB - 1] * NL
+            alt = [(-HB if (i // H + i) % 2 else HB - 1) for i in range(NL)]
+            cs = [lo, hi, alt, [-v - 1 for v in alt], bal_limbs(51 * p // 100, NL), bal_limbs(-(51 * p // 100), NL), bal_limbs(0, NL)]
+            cs += [bal_limbs(rng.randrange(-p // 2, p // 2), NL) for _ in range(3)]
+            for red in (0, 15 | VF | VFM | VFS, KMRB_RED):
+                for i, a in enumerate(cs):
+                    b, c, d = cs[(i + 1) % len(cs)], cs[(i + 3) % len(cs)], cs[(i + 5) % len(cs)]
+                    sqr_kara_bal(a, b, p, st, red)
+                    mul_kara_bal(a, b, c, d, p, st, red)
+            a, b = cs[4], cs[5]
+            c, d = cs[-1], cs[-2]
+            for _ in range(6):
+                a, b = sqr_kara_bal(a, b, p, st)
+                a, b = mul_kara_bal(a, b, c, d, p, st)
+                assert in_lazy_range(a, p) and in_lazy_range(b, p)
+    return st
+
+
 def random_prime(bits, rng):
     while True:
         c = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
@@ -397,5 +753,8 @@ if __name__ == "__main__":
     run(rounds, red=KMR_RED)
     r = run(rounds, red=15 | VF | VFM)
     print({"red_max_rq_log2": r.max_rq.bit_length(), "red_max_e_log2": r.max_red_e.bit_length(), "red_max_d_log2": r.max_d.bit_length()})
+    bst = run_bal(rounds)
+    print({"bal_max_d_log2": bst.max_d.bit_length(), "bal_max_v_log2": bst.max_v.bit_length(), "bal_max_u_log2": bst.max_u.bit_length(),
+           "bal_max_e_log2": bst.max_e.bit_length(), "bal_red_macs": bst.red_macs})
     print({"max_col_log2": s.max_col.bit_length(), "max_cc_log2": s.max_cc.bit_length(),
            "max_d_log2": s.max_d.bit_length(), "max_running_log2": s.max_run.bit_length(), "max_mid_cell_log2": s.max_e.bit_length()})
