@@ -73,8 +73,9 @@ int pai_profile_last(int index, char* name_out, size_t name_cap, float* ms_out);
 /* The kernel family behind entry i where one name covers several ("pp", "rl", "window", "pair4", "padic", "padic_kara_mul", "pair",
  * "wide", "lane_group", "lat", ...; "" where the name says it all): what a test asserts after forcing a path with PAI_TUNE / PAI_DISABLE. */
 int pai_profile_last_path(int index, char* path_out, size_t path_cap);
-/* The kernel within that family where several share one path name: "kmrb", "kmr" or "km" for the register-resident 36-limb
- * decrypt kernels behind "padic_kara_mul" (balanced digits / Karatsuba quotient products / schoolbook ones), "" elsewhere. */
+/* The kernel within that family where several share one path name: "kmrb", "kmrb2s", "kmr" or "km" for the register-resident 36-limb
+ * decrypt kernels behind "padic_kara_mul" (balanced digits with one stored sum per column, the default / with two / Karatsuba
+ * quotient products on unsigned limbs / schoolbook ones), "" elsewhere. */
 int pai_profile_last_mode(int index, char* mode_out, size_t mode_cap);
 
 /* ---- device memory helpers (for callers that do not bring their own allocator) ---------------- */

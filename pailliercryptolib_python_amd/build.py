@@ -37,6 +37,7 @@ SOURCES = [
     "padic_dec_kernels.hip",
     "padic_dec_kmr_kernels.hip",
     "padic_dec_kmrb_kernels.hip",
+    "padic_dec_kmrbs_kernels.hip",
     "padic_enc_kernels.hip",
     "padic_enc36_kernels.hip",
     "pair_kernels.hip",

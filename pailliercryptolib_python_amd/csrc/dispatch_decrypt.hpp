@@ -454,11 +454,12 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
             const bool mul_kara = !knob_disabled("padic_kara_mul");  // PAI_DISABLE=padic_kara_mul: row-wise products, LDS hand-over
             const bool red_kara = sqr_kara && mul_kara && !knob_disabled("padic_kara_red");   // PAI_DISABLE=padic_kara_red: schoolbook quotient products (the PADIC_LDS_KM kernel)
             const bool bal_kara = red_kara && !knob_disabled("padic_balanced");   // PAI_DISABLE=padic_balanced: unsigned limbs, two carry streams per column (the PADIC_LDS_KMR kernel)
+            const bool one_sum = bal_kara && !knob_disabled("padic_one_sum");   // PAI_DISABLE=padic_one_sum: two stored sums per column, V_k and U_k (the PADIC_LDS_KMRB kernel)
             // (36 limbs: squarings, products and the quotient products of their reductions by Karatsuba columns unless PAI_DISABLE says
             // otherwise; the other limb counts row-wise.  The path name of the first two register-resident kernels is the same.)
             const char* padic_path = sk->padic_nl != 36 ? "padic" : (!sqr_kara ? "padic_rowwise" : (mul_kara ? "padic_kara_mul" : "padic_kara"));
             ScopedKernelTimer t("k_dec_a", s, sk->padic_nl ? padic_path : (sk->wide_nl ? "wide" : "lane_group"));
-            if (sk->padic_nl == 36 && sqr_kara && mul_kara) t.mode = bal_kara ? "kmrb" : (red_kara ? "kmr" : "km");
+            if (sk->padic_nl == 36 && sqr_kara && mul_kara) t.mode = one_sum ? "kmrb" : (bal_kara ? "kmrb2s" : (red_kara ? "kmr" : "km"));
             if (sk->padic_nl) {
                 DecPadicParams Q;
                 for (int w = 0; w < 2; ++w) {
@@ -477,6 +478,7 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
                 Q.mul_kara = mul_kara;
                 Q.red_kara = red_kara;
                 Q.bal_kara = bal_kara;
+                Q.one_sum = one_sum;
                 if (!launch_dec_a_padic(sk->padic_nl, s, gridx, Q, d_ct, sk->ubuf.as<uint32_t>(), (int)N, sk->table.as<uint32_t>()))
                     throw PaiError(PAI_E_INTERNAL, "no p-adic kernel for this limb count");
             } else if (sk->wide_nl) {

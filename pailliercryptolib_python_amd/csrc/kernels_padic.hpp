@@ -22,7 +22,10 @@ struct DecPadicParams {
     int sqr_kara;                // 36-limb primes: squarings by sqr_kara (MODE PADIC_LDS_K) instead of the row-wise sqr
     int mul_kara;                // ... and the products too, digits kept in registers between operations (MODE PADIC_LDS_KM)
     int red_kara;                // ... and the quotient products of the reductions (MODE PADIC_LDS_KMR); needs mul_kara
-    int bal_kara;                // ... on balanced digits, one carry stream per column (MODE PADIC_LDS_KMRB); needs red_kara
+    int16_t bal_kara;            // ... on balanced digits, one carry stream per column (MODE PADIC_LDS_KMRB); needs red_kara
+    int16_t one_sum;             // ... with one stored sum per column for both streams (MODE PADIC_LDS_KMRBS); needs bal_kara
+                                 // (two halves of one word: the structure is a kernel argument and keeps its size, so the
+                                 // kernels of the other modes keep their code objects)
 };
 
 // (A, B) <- Montgomery digit form of the packed integer `row` (row_words 32-bit words, any value < s^2 R-ish):
@@ -114,7 +117,11 @@ constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 //                   signed 64-bit cell — one carry stream, one shift and one digit extraction per column, no 128-bit cell.
 //                   The table holds the balanced limbs as they are (same format and size); the row-wise entry and exit are
 //                   those of the other modes, with one carry pass per digit on either side.
-constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4, PADIC_LDS_KMRB = 5;
+// MODE PADIC_LDS_KMRBS: PADIC_LDS_KMRB with ONE stored sum per column, S_k = [2] V_k + U_k, for the product stream and the quotient
+//                   stream together in both passes of a squaring and the first pass of a product (mont_padic.hpp: kara_pass_bal,
+//                   ONES; PADIC_KMRBS_RED).  Same digits, quotient digits and carries, same LDS, same table.
+constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4, PADIC_LDS_KMRB = 5,
+              PADIC_LDS_KMRBS = 6;
 constexpr bool padic_reg_mode(int mode) { return mode == PADIC_LDS_KM || mode == PADIC_LDS_KMR; }
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
@@ -175,7 +182,8 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         const uint32_t* row = ct + (size_t)es * P.ct_words;
         // ---- digit form of ct:  sum_i  (c_i, 0) * digits(R^(i+2) mod s^2) -----------------------------
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
-        if constexpr (MODE == PADIC_LDS_KMRB) {
+        if constexpr (MODE == PADIC_LDS_KMRB || MODE == PADIC_LDS_KMRBS) {
+            constexpr int BRED = MODE == PADIC_LDS_KMRBS ? E::PADIC_KMRBS_RED : E::PADIC_KMRB_RED;
             // ---- the loop of PADIC_LDS_KM / PADIC_LDS_KMR below (same steps, same table slots) on balanced digits --------
             const int NT = P.tbl_entries;
             int32_t nb[NL];                               // balanced modulus limbs: wave-uniform, formed once from the SGPR copy
@@ -208,9 +216,9 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
                 }
                 if (t == NT - 1) get_e = i0;
 #pragma unroll 1
-                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<E::PADIC_KMRB_RED>(a, b, nb, n0inv);
+                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<BRED>(a, b, nb, n0inv);
                 if (idx != 0xFF)
-                    E::template mul_kara_reg_bal<E::PADIC_KMRB_RED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
+                    E::template mul_kara_reg_bal<BRED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
                 if (put_e >= 0) put(put_e);
                 if (get_e >= 0) {
 #pragma unroll

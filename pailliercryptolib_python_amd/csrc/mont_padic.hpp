@@ -1006,7 +1006,7 @@ struct Padic {
     // products is one chain V_k as well.  Cells: tools/kara_model.py (kara_pass_bal).
     PAI_DEV static int32_t sfield(uint32_t v) { return (int32_t)(v << (32 - RB)) >> (32 - RB); }
     PAI_DEV static uint64_t smul(int32_t a, int32_t b) { return (uint64_t)((int64_t)a * (int64_t)b); }
-    template <int FORM, bool KRED = false, bool VF = false>
+    template <int FORM, bool KRED = false, bool VF = false, int ONES = 0>
     PAI_DEV static void kara_pass_bal(int32_t (&out)[NL], int32_t (&mq)[NL], const int32_t (&x)[NL], const int32_t (&y)[NL],
                                       const int32_t (&x2)[NL], const int32_t (&y2)[NL], const int32_t (&min)[NL],
                                       const int32_t* __restrict__ nm, uint32_t n0inv) {
@@ -1050,6 +1050,109 @@ struct Padic {
         // the compiler emits sign extension, subtract and borrow (three instructions, 36 columns)
         const int32_t neg1 = -(int32_t)(n0inv & 1u);
         uint64_t carry = 0;
+        if constexpr (ONES != 0 && KRED && VF && !SUM) {
+            // ONE stored sum per column.  V_k and U_k are both kept for H columns and both enter column k and column k + H, never
+            // apart: S_k = [2] V_k + U_k is all that is needed, and the column is
+            //        d_k = S_k + S_(k-H) - [2] D_(k-H) - E_(k-H) - min_k + carry,
+            // H live 64-bit sums instead of 2 H and two joining additions per column instead of four.  The chains of V and U run
+            // on one register (the first multiply-add of U takes the finished [2] V_k as its addend); the doubled pass takes the
+            // doubled right operand (yd, dy2) instead of shifting the column.  What does not wait for the previous column
+            // (S_(k-H), -D, -E, -min) is one chain e; s joins it, the carry comes last.  S_k is used modulo 2^64 only; d_k is the
+            // same integer as in the two-sum form, so mq, out and carry are bit for bit the same.  ONES == 1: the terms of the
+            // newest digit mq[k - 1] go onto s before the column is formed; ONES == 2: onto s and onto the column, one
+            // multiply-add more and s off the column's dependency chain.  Cells: tools/kara_model.py (ones).
+            constexpr int NU = H + NP;                    // S_0 .. S_(NU-1)
+            uint64_t ss[NU];
+#pragma unroll
+            for (int k = 0; k < 2 * NL - 1; ++k) {
+                const bool mid = k >= H && k - H < NP;
+                const int j = k - H;
+                uint64_t s = 0, off = 0;
+                if (k < NP) {
+                    const int lo = k < H ? 0 : k - H + 1, hi = k < H ? k : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = k - i;
+                        if (DBL) s += smul(x[i], yd[l]);
+                        else if (!SYM) s += smul(x[i], y[l]);
+                        else if (i < l) off += smul(x[i], y[l]);
+                        else if (i == l) s += smul(x[i], y[i]);
+                    }
+                }
+                if (mid) {
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (DBL) s += smul(x[H + i], yd[H + l]);
+                        else if (!SYM) s += smul(x[H + i], y[H + l]);
+                        else if (i < l) off += smul(x[H + i], y[H + l]);
+                        else if (i == l) s += smul(x[H + i], y[H + i]);
+                    }
+                }
+                if (SYM) s += off << 1;
+                // quotient terms of the digits known before the previous column
+                if (k < NP) {
+                    const int lo0 = k < H ? 0 : k - H + 1, hi0 = k < H ? k - 1 : H - 1;
+#pragma unroll
+                    for (int i = lo0; i <= hi0; ++i)
+                        if (i != k - 1) s += smul(mq[i], nm[k - i]);
+                }
+                if (mid) {
+                    const int lo2 = j < H ? 0 : j - H + 1, hi2 = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo2; i <= hi2; ++i)
+                        if (!(i == j && k < NL) && H + i != k - 1) s += smul(mq[H + i], nm[H + j - i]);
+                }
+                // the one term of the newest digit: mq[k-1] nm[1] (in Q0_k) or mq[k-1] nm[H+1] (in Q2_(k-H))
+                const bool newest = k >= 1 && k <= NL;
+                const int nn = k <= H ? 1 : H + 1;
+                if (ONES == 1 && newest) s += smul(mq[k - 1], nm[nn]);
+                // what does not wait for the previous column's carry
+                uint64_t e = k >= H ? ss[k - H] : 0;
+                if (mid) {
+                    uint64_t nd = 0;
+                    const int lo = j < H ? 0 : j - H + 1, hi = j < H ? j : H - 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        const int l = j - i;
+                        if (DBL) e += smul(nx[i], dy2[l]);
+                        else if (!SYM) e += smul(nx[i], dy[l]);
+                        else if (i < l) nd += smul(nx[i], dy[l]);
+                        else if (i == l) e += smul(nx[i], dy[i]);
+                    }
+                    if (SYM) e += nd << 1;
+#pragma unroll
+                    for (int i = lo; i <= hi; ++i) {
+                        if (i == j && k < NL) e += smul(mq[i], ndp[0]);
+                        else if (H + i != k - 1) e += smul(dm[i], ndp[j - i]);
+                    }
+                }
+                if (SECOND && k < NL) e += smul(min[k], neg1);
+                if (k - 1 >= H && k - 1 < NL) e += smul(dm[k - 1 - H], ndp[1]);
+                uint64_t d = e + s + carry;
+                if (ONES == 2 && newest) {
+                    s += smul(mq[k - 1], nm[nn]);
+                    d += smul(mq[k - 1], nm[nn]);
+                }
+                if (k < NL) {
+                    mq[k] = sfield((uint32_t)d * n0inv);
+                    d += smul(mq[k], nm[0]);
+                    if (k < H) {
+                        s += smul(mq[k], nm[0]);
+                    } else {
+                        s += smul(mq[k], nm[H]);
+                        dm[k - H] = mq[k - H] - mq[k];
+                    }
+                } else {
+                    out[k - NL] = sfield((uint32_t)d);
+                }
+                if (k < NU) ss[k] = s;
+                carry = (uint64_t)((int64_t)(k < NL ? d : d + (1ull << (RB - 1))) >> RB);
+            }
+            out[NL - 1] = (int32_t)carry;
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < 2 * NL - 1; ++k) {
             uint64_t t = 0;                               // the product column X_k, exact modulo 2^64
@@ -1186,12 +1289,22 @@ struct Padic {
     // reduction by U_k on top was not faster in the unsigned form (profiles/r14/) and costs registers here (profiles/r15/)
     static constexpr int KRED_VFS = 64;
     static constexpr int PADIC_KMRB_RED = PADIC_KMR_RED | KRED_VFS;
+    // KRED_ONES = the passes that have both KRED and VF (both of a squaring, the first of a product) keep ONE stored sum per
+    // column, S_k = [2] V_k + U_k (kara_pass_bal: ONES); KRED_ONES2 on top = the terms of the newest quotient digit are added
+    // to the sum and to the column separately.  Kernel mode PADIC_LDS_KMRBS.  The second pass of a product keeps its form: with
+    // Karatsuba quotient products and one sum it is shorter by itself, but the squaring in the same loop grows.
+    static constexpr int KRED_ONES = 128, KRED_ONES2 = 256;
+#ifndef PAI_KMRBS_NEWEST_TWICE
+#define PAI_KMRBS_NEWEST_TWICE 0      // 1: build the other placement of the newest digit's terms (profiles/r17/README.md)
+#endif
+    static constexpr int PADIC_KMRBS_RED = PADIC_KMRB_RED | KRED_ONES | (PAI_KMRBS_NEWEST_TWICE ? KRED_ONES2 : 0);
+    static constexpr int ones(int RED) { return (RED & KRED_ONES) ? ((RED & KRED_ONES2) ? 2 : 1) : 0; }
     template <int RED = 0>
     PAI_DEV static void sqr_kara_reg_bal(int32_t (&a)[NL], int32_t (&b)[NL], const int32_t* __restrict__ nm, uint32_t n0inv) {
         constexpr bool VF = (RED & KRED_VF) != 0;
         int32_t m[NL], w[NL], m2[NL], v[NL];
-        kara_pass_bal<KARA_SQR, kred(RED, KARA_SQR), VF>(w, m, a, a, a, a, m, nm, n0inv);
-        kara_pass_bal<KARA_SQR2, kred(RED, KARA_SQR2), VF>(v, m2, a, b, a, b, m, nm, n0inv);
+        kara_pass_bal<KARA_SQR, kred(RED, KARA_SQR), VF, ones(RED)>(w, m, a, a, a, a, m, nm, n0inv);
+        kara_pass_bal<KARA_SQR2, kred(RED, KARA_SQR2), VF, ones(RED)>(v, m2, a, b, a, b, m, nm, n0inv);
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }
@@ -1204,7 +1317,7 @@ struct Padic {
             const uint4 t = rsrc(0, ch);
             c[4 * ch] = (int32_t)t.x; c[4 * ch + 1] = (int32_t)t.y; c[4 * ch + 2] = (int32_t)t.z; c[4 * ch + 3] = (int32_t)t.w;
         }
-        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0>(w, m, a, c, a, c, m, nm, n0inv);
+        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0, ones(RED)>(w, m, a, c, a, c, m, nm, n0inv);
 #pragma unroll
         for (int ch = 0; ch < NC; ++ch) {
             const uint4 t = rsrc(1, ch);

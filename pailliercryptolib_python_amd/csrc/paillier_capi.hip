@@ -406,6 +406,8 @@ struct ScopedKernelTimer {
 //                                  padic_kara_red (36-limb decrypt: quotient products of the Montgomery reductions schoolbook, kernel mode PADIC_LDS_KM),
 //                                  padic_balanced (36-limb decrypt: unsigned limbs with two carry streams per column, kernel mode PADIC_LDS_KMR,
 //                                  instead of balanced digits, PADIC_LDS_KMRB),
+//                                  padic_one_sum (36-limb decrypt: two stored sums per column, V_k of the product stream and U_k of the
+//                                  quotient stream, kernel mode PADIC_LDS_KMRB, instead of the one sum S_k of PADIC_LDS_KMRBS),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch),
 //                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key)

@@ -356,6 +356,19 @@ def sqr_kara(a, b, p, NL, st, in_range=True, red=0):
 VFS = 64                              # mul_kara_reg_bal<RED>: the second pass of a product (sum of two products) as one chain too
 KMRB_RED = KMR_RED | VFS              # Padic::PADIC_KMRB_RED: what kernel mode PADIC_LDS_KMRB runs
 HB = B >> 1                           # 2^28
+# One stored sum per column (kernel mode PADIC_LDS_KMRBS): the passes with both kred and vf (both of a squaring, the first of a
+# product) keep S_k = [2] V_k + U_k instead of V_k and U_k; the column is S_k + S_(k-H) - [2] D_(k-H) - E_(k-H) - min_k + carry.
+# The model runs that pass in 64-bit cells that WRAP (S_k is needed modulo 2^64 only: [2] V_k + U_k can pass 2^63) and asserts
+# that the finished column, read as a signed 64-bit integer, is the schoolbook column.  ONES2 on top: the terms of the newest
+# quotient digit go onto the sum and onto the column separately instead of onto the sum before the column is formed.
+ONES, ONES2 = 128, 256
+KMRBS_RED = KMRB_RED | ONES           # Padic::PADIC_KMRBS_RED: what kernel mode PADIC_LDS_KMRBS runs
+M64 = (1 << 64) - 1
+
+
+def red_ones(red):
+    """Padic::ones(RED): 0 = two stored sums, 1 / 2 = one, the newest digit's terms once / twice."""
+    return (2 if red & ONES2 else 1) if red & ONES else 0
 
 
 def sfield(v):
@@ -406,8 +419,8 @@ class BalStats:
         self.red_macs = 0
 
 
-def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False):
-    """One pass of kara_pass_bal<FORM, KRED, VF> on signed limb lists; returns (out limbs, quotient limbs)."""
+def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False, ones=0):
+    """One pass of kara_pass_bal<FORM, KRED, VF, ONES> on signed limb lists; returns (out limbs, quotient limbs)."""
     form = int(form)
     sym, dbl, summ = form == SQR, form == SQR2, form == MUL2
     second = dbl or summ
@@ -464,8 +477,113 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
     mq, out = [0] * NL, [0] * NL
     carry = 0
     macs = 0
+    ones = ones if kred and vf and not summ else 0      # as the kernel: the other passes keep their form
+    ss = [0] * (H + NP)                                 # ones: S_k, 64-bit cells
+
+    def finish(k, d, school):
+        """The finished column: the schoolbook one, inside a signed 64-bit cell; only now it is shifted.  Returns the carry."""
+        assert d == school + (mq[k] * nm[0] if k < NL else 0), (k, d, school)
+        assert -(1 << 63) <= d and d + HB < (1 << 63), "finished column leaves int64"
+        st.max_d = max(st.max_d, abs(d))
+        if k < NL:
+            assert -HB <= mq[k] < HB and d % B == 0
+            return d >> RB
+        assert -HB <= out[k - NL] < HB
+        c = (d + HB) >> RB
+        assert c * B + out[k - NL] == d
+        return c
+
     for k in range(2 * NL - 1):
         mid = H <= k < H + NP
+        if ones:
+            # every cell below is a 64-bit word that wraps; only the finished column is read as a signed integer
+            j = k - H
+            s = off = 0
+            for o, jj, on in ((0, k, k < NP), (H, j, mid)):
+                if not on:
+                    continue
+                lo, hi = rng(jj)
+                for i in range(lo, hi + 1):
+                    l = jj - i
+                    if dbl:
+                        s = (s + smul(x[o + i], yd[o + l])) & M64
+                    elif not sym:
+                        s = (s + smul(x[o + i], y[o + l])) & M64
+                    elif i < l:
+                        off = (off + smul(x[o + i], y[o + l])) & M64
+                    elif i == l:
+                        s = (s + smul(x[o + i], y[o + i])) & M64
+            if sym:
+                s = (s + (off << 1)) & M64
+            if k < NP:
+                lo0, hi0 = (0, k - 1) if k < H else (k - H + 1, H - 1)
+                for i in range(lo0, hi0 + 1):
+                    if i != k - 1:
+                        s = (s + smul(mq[i], nm[k - i])) & M64
+                        macs += 1
+            if mid:
+                lo2, hi2 = rng(j)
+                for i in range(lo2, hi2 + 1):
+                    if not (i == j and k < NL) and H + i != k - 1:
+                        s = (s + smul(mq[H + i], nm[H + j - i])) & M64
+                        macs += 1
+            newest = 1 <= k <= NL
+            nn = 1 if k <= H else H + 1
+            if ones == 1 and newest:
+                s = (s + smul(mq[k - 1], nm[nn])) & M64
+                macs += 1
+            e = ss[k - H] if k >= H else 0
+            if mid:
+                nd = 0
+                lo, hi = rng(j)
+                for i in range(lo, hi + 1):
+                    l = j - i
+                    if dbl:
+                        e = (e + smul(nx[i], dy2[l])) & M64
+                    elif not sym:
+                        e = (e + smul(nx[i], dy[l])) & M64
+                    elif i < l:
+                        nd = (nd + smul(nx[i], dy[l])) & M64
+                    elif i == l:
+                        e = (e + smul(nx[i], dy[i])) & M64
+                if sym:
+                    e = (e + (nd << 1)) & M64
+                for i in range(lo, hi + 1):
+                    if i == j and k < NL:
+                        e = (e + smul(mq[i], ndp[0])) & M64
+                        macs += 1
+                    elif H + i != k - 1:
+                        e = (e + smul(dm[i], ndp[j - i])) & M64
+                        macs += 1
+            if second and k < NL:
+                e = (e + smul(mnin[k], -1)) & M64
+            if H <= k - 1 < NL:
+                e = (e + smul(dm[k - 1 - H], ndp[1])) & M64
+                macs += 1
+            d = (e + s + carry) & M64
+            if ones == 2 and newest:
+                s = (s + smul(mq[k - 1], nm[nn])) & M64
+                d = (d + smul(mq[k - 1], nm[nn])) & M64
+                macs += 2
+            lo, hi = (0, k - 1) if k < NL else (k - NL + 1, NL - 1)
+            want = column(x, y, k)
+            school = (2 * want if dbl else want) - (mnin[k] if second and k < NL else 0) + carry + sum(mq[i] * nm[k - i] for i in range(lo, hi + 1))
+            if k < NL:
+                mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+                d = (d + smul(mq[k], nm[0])) & M64
+                s = (s + smul(mq[k], nm[0 if k < H else H])) & M64
+                macs += 2
+                if k >= H:
+                    dm[k - H] = mq[k - H] - mq[k]
+                    assert i32(dm[k - H])
+            else:
+                out[k - NL] = sfield(d)
+            if k < H + NP:
+                ss[k] = s
+            else:
+                assert s == 0
+            carry = finish(k, d - (1 << 64) if d >> 63 else d, school)
+            continue
         t = 0
         if vf:
             vk = off = nd = 0
@@ -612,17 +730,7 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
                 ru[k] = u
             else:
                 assert u == 0
-        # the finished column: the schoolbook one, inside a signed 64-bit cell; only now it is shifted
-        assert d == school + (mq[k] * nm[0] if k < NL else 0), (k, d, school)
-        assert -(1 << 63) <= d and d + HB < (1 << 63), "finished column leaves int64"
-        st.max_d = max(st.max_d, abs(d))
-        if k < NL:
-            assert -HB <= mq[k] < HB and d % B == 0
-            carry = d >> RB
-        else:
-            assert -HB <= out[k - NL] < HB
-            carry = (d + HB) >> RB
-            assert carry * B + out[k - NL] == d
+        carry = finish(k, d, school)
     assert i32(carry)
     out[NL - 1] = carry
     st.red_macs = macs
@@ -640,7 +748,7 @@ def mul_kara_bal(al, bl, cl, dl, p, st, red=KMRB_RED):
     R = 1 << (RB * NL)
     nm, n0inv = _bal_ctx(p, NL)
     assert value(nm) == p
-    w, m = kara_pass_bal(MUL, al, cl, [0] * NL, nm, n0inv, st, kred=bool(red >> MUL & 1), vf=bool(red & VFM))
+    w, m = kara_pass_bal(MUL, al, cl, [0] * NL, nm, n0inv, st, kred=bool(red >> MUL & 1), vf=bool(red & VFM), ones=red_ones(red))
     v, m2 = kara_pass_bal(MUL2, al, dl, m, nm, n0inv, st, x2=bl, y2=cl, kred=bool(red >> MUL2 & 1), vf=bool(red & VFS))
     a, b, c, d = value(al), value(bl), value(cl), value(dl)
     W, M, V, M2 = value(w), value(m), value(v), value(m2)
@@ -657,8 +765,8 @@ def sqr_kara_bal(al, bl, p, st, red=KMRB_RED):
     NL = len(al)
     R = 1 << (RB * NL)
     nm, n0inv = _bal_ctx(p, NL)
-    w, m = kara_pass_bal(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF))
-    v, m2 = kara_pass_bal(SQR2, al, bl, m, nm, n0inv, st, kred=bool(red >> SQR2 & 1), vf=bool(red & VF))
+    w, m = kara_pass_bal(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF), ones=red_ones(red))
+    v, m2 = kara_pass_bal(SQR2, al, bl, m, nm, n0inv, st, kred=bool(red >> SQR2 & 1), vf=bool(red & VF), ones=red_ones(red))
     a, b = value(al), value(bl)
     W, M, V, M2 = value(w), value(m), value(v), value(m2)
     assert W * R == a * a + M * p
@@ -684,7 +792,7 @@ def run_bal(rounds=1, seed=2):
             alt = [(-HB if (i // H + i) % 2 else HB - 1) for i in range(NL)]
             cs = [lo, hi, alt, [-v - 1 for v in alt], bal_limbs(51 * p // 100, NL), bal_limbs(-(51 * p // 100), NL), bal_limbs(0, NL)]
             cs += [bal_limbs(rng.randrange(-p // 2, p // 2), NL) for _ in range(3)]
-            for red in (0, 15 | VF | VFM | VFS, KMRB_RED):
+            for red in (0, 15 | VF | VFM | VFS, KMRB_RED, KMRBS_RED, KMRBS_RED | ONES2):
                 for i, a in enumerate(cs):
                     b, c, d = cs[(i + 1) % len(cs)], cs[(i + 3) % len(cs)], cs[(i + 5) % len(cs)]
                     sqr_kara_bal(a, b, p, st, red)
