@@ -416,6 +416,8 @@ def from_balanced_plus_p(x, nb, less):
 class BalStats:
     def __init__(self):
         self.max_d = self.max_v = self.max_u = self.max_e = 0
+        self.max_c = 0                        # largest |carry| out of a finished column
+        self.at_d = None                      # (form, column) of the largest finished column
         self.red_macs = 0
 
 
@@ -442,14 +444,16 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
     vbound = (2 if summ else 1) * H << 56
     dbound = (2 if summ else 1) * H << 58
 
-    def smul(a, b):
-        assert i32(a) and i32(b)
-        pr = a * b
-        assert -(1 << 63) <= pr < (1 << 63)
-        return pr
+    def smul(a, b, T=1 << 31):
+        assert -T <= a < T and -T <= b < T               # two int32: the product fits int64
+        return a * b
 
     def rng(j):
         return (0, j) if j < H else (j - H + 1, H - 1)
+
+    def dot(xx, yy, lo, hi, k):
+        """sum of xx[i] yy[k - i] over lo <= i <= hi (the reference sums: plain integers)"""
+        return sum(map(int.__mul__, xx[lo:hi + 1], yy[k - hi:k - lo + 1][::-1]))
 
     def half(o, j):
         s = 0
@@ -468,7 +472,7 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
         return s
 
     def column(xx, yy, k):
-        return sum(xx[i] * yy[k - i] for i in range(max(0, k - NL + 1), min(k, NL - 1) + 1))
+        return dot(xx, yy, max(0, k - NL + 1), min(k, NL - 1), k)
 
     p0, p2 = [0] * NP, [0] * NP
     pv = [0] * (H + NP)
@@ -484,13 +488,16 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
         """The finished column: the schoolbook one, inside a signed 64-bit cell; only now it is shifted.  Returns the carry."""
         assert d == school + (mq[k] * nm[0] if k < NL else 0), (k, d, school)
         assert -(1 << 63) <= d and d + HB < (1 << 63), "finished column leaves int64"
-        st.max_d = max(st.max_d, abs(d))
+        if abs(d) > st.max_d:
+            st.max_d, st.at_d = abs(d), (form, k)
         if k < NL:
             assert -HB <= mq[k] < HB and d % B == 0
-            return d >> RB
-        assert -HB <= out[k - NL] < HB
-        c = (d + HB) >> RB
-        assert c * B + out[k - NL] == d
+            c = d >> RB
+        else:
+            assert -HB <= out[k - NL] < HB
+            c = (d + HB) >> RB
+            assert c * B + out[k - NL] == d
+        st.max_c = max(st.max_c, abs(c))
         return c
 
     for k in range(2 * NL - 1):
@@ -567,7 +574,7 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
                 macs += 2
             lo, hi = (0, k - 1) if k < NL else (k - NL + 1, NL - 1)
             want = column(x, y, k)
-            school = (2 * want if dbl else want) - (mnin[k] if second and k < NL else 0) + carry + sum(mq[i] * nm[k - i] for i in range(lo, hi + 1))
+            school = (2 * want if dbl else want) - (mnin[k] if second and k < NL else 0) + carry + dot(mq, nm, lo, hi, k)
             if k < NL:
                 mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
                 d = (d + smul(mq[k], nm[0])) & M64
@@ -657,7 +664,7 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
         if second and k < NL:
             d += smul(mnin[k], -1)
         lo, hi = (0, k - 1) if k < NL else (k - NL + 1, NL - 1)
-        school = d + carry + sum(mq[i] * nm[k - i] for i in range(lo, hi + 1))
+        school = d + carry + dot(mq, nm, lo, hi, k)
         if not kred:
             macs += hi - lo + 1 + (1 if k < NL else 0)
             d = school
