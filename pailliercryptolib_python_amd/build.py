@@ -39,6 +39,7 @@ SOURCES = [
     "padic_dec_kmrb_kernels.hip",
     "padic_dec_kmrbs_kernels.hip",
     "padic_enc_kernels.hip",
+    "padic_enc_kara_kernels.hip",
     "padic_enc36_kernels.hip",
     "pair_kernels.hip",
     "crt_lift_kernels.hip",

@@ -169,12 +169,17 @@ static void encrypt_common(const pai_pubkey* pk, const uint32_t* d_m, const uint
         Q.fb_windows = pk->fbd_windows;
         Q.fb_wbits = pk->fbd_wbits;
         Q.fb_gform = pk->fb_gform ? 1 : 0;
+        // DJN encryption at 72 limbs on a g-factored table: Karatsuba columns on a register-held digit pair
+        // (PAI_DISABLE=enc_kara: the row-wise product kernel)
+        const bool enc_kara = from_plain && d_r && pk->penc_nl == 72 && pk->fb_gform && padic_enc_gform_supported() && !knob_disabled("enc_kara");
+        Q.enc_kara = enc_kara ? 1 : 0;
         Q.pt_words = pk->n_words;
         Q.ct_words = pk->ct_words;
         Q.r_words = pk->r_words;
         const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
         const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
         ScopedKernelTimer t(!from_plain ? "k_encrypt(obfuscate)" : (d_r ? "k_encrypt(djn)" : "k_encrypt(raw)"), s, "padic");
+        if (from_plain && d_r) t.mode = enc_kara ? "enc_kara" : "rows";
         launcher(padic_enc_ops(pk->penc_nl), &PadicEncOps::encrypt, "no digit-engine encrypt kernel for this limb count")(
             s, pgrid, Q, d_m, d_r, d_ct_in, d_ct_out, (int)N, !from_plain ? 2 : (d_r ? 1 : 0));
         t.stop();

@@ -36,6 +36,7 @@ struct EncPadicParams {
     int fb_windows, fb_wbits;
     int pt_words, ct_words, r_words;
     int fb_gform;                // g-factored table (round 4): entry = (a, t) with x R == a (1 + t n) (mod n^2), see k_fb_g_*
+    int enc_kara = 0;            // DJN encryption at 72 limbs on a g-factored table: the Karatsuba-column kernel (k_encrypt_padic: KARA)
 };
 
 // the g-factored product runs on the fused product rule of both encryption kernels
@@ -402,7 +403,11 @@ PAI_DEV uint32_t lds_limb(const uint4* A, const uint4* B, int J) {
 
 // OBF = true is the apply_obfuscator instantiation (mode 2 only): kept out of the encryption kernel, whose register
 // allocation suffers from the extra digit-form conversion (k_encrypt 67 -> 78 ms per 2^20 when both shared one kernel)
-template <int NL, int U, bool OBF, bool GFORM>
+// KARA = true (NL = 72, OBF = false, GFORM = true, mode 1; own translation unit padic_enc_kara_kernels.hip): the table products
+// run on a balanced digit pair that stays in registers from the first entry to the last window, by Karatsuba columns in two
+// half-width steps (mont_padic.hpp: mul_kara2_c0_bal) — 16 128 multiply-adds executed per product instead of 20 736.  The exponents t
+// are summed in this lane's LDS digit buffer A, which the register loop leaves free; the row-wise exit is the same.
+template <int NL, int U, bool OBF, bool GFORM, bool KARA = false>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
 k_encrypt_padic(EncPadicParams P, const uint32_t* __restrict__ m, const uint32_t* __restrict__ r,
                 const uint32_t* ct_in, uint32_t* ct_out, int n, int mode) {            // ct_out is ct_in under pai_obfuscate
@@ -454,6 +459,128 @@ k_encrypt_padic(EncPadicParams P, const uint32_t* __restrict__ m, const uint32_t
             // right operand without a second digit and the exponents t are summed lazily in registers (limbs < 2^29, at
             // most 7 additions between carry passes); g^(m + sum t) joins in the final product with the plain pair (1, s)
             uint32_t tsum[GFORM ? NL : 1];
+            if constexpr (KARA) {
+                static_assert(!KARA || (GFORM && !OBF && NL % 8 == 0), "the g-factored table product of DJN encryption");
+                constexpr int HC = E::NC / 2;                 // chunks of half an entry
+                int32_t nb[NL], ndp[NL / 2];                  // balanced modulus limbs and their half differences: wave-uniform
+                E::to_balanced(sn, nb);
+#pragma unroll
+                for (int l = 0; l < NL / 4; ++l) {
+                    ndp[l] = nb[NL / 4 + l] - nb[l];
+                    ndp[NL / 4 + l] = nb[3 * (NL / 4) + l] - nb[NL / 2 + l];
+                }
+                auto entry = [&](int jw) -> const uint4* {
+                    const int bit = jw * P.fb_wbits, k = bit >> 5;
+                    uint64_t bits2 = rrow[k];
+                    if (k + 1 < P.r_words) bits2 |= (uint64_t)rrow[k + 1] << 32;
+                    const uint32_t d = (uint32_t)(bits2 >> (bit & 31)) & ((1u << P.fb_wbits) - 1u);
+                    return P.fb_table + (((size_t)jw << P.fb_wbits) + d) * 2 * E::NC;
+                };
+                auto half_limbs = [&](const uint4 (&raw)[HC], uint32_t (&u)[NL / 2]) {
+#pragma unroll
+                    for (int c = 0; c < HC; ++c) { u[4 * c] = raw[c].x; u[4 * c + 1] = raw[c].y; u[4 * c + 2] = raw[c].z; u[4 * c + 3] = raw[c].w; }
+                };
+                auto fetch_half = [&](const uint4* ent, int h, uint4 (&raw)[HC]) {
+#pragma unroll
+                    for (int c = 0; c < HC; ++c) raw[c] = ent[HC * h + c];
+                };
+                // tsum += t of the entry, in LDS; a carry pass after every sixth addition (limbs < 7 * 2^29 + carry: no 32-bit wrap)
+                int since_norm = 0;
+                auto add_t = [&](const uint4* ent, bool first) {
+#pragma unroll 1
+                    for (int c = 0; c < E::NC; ++c) {
+                        uint4 t = ent[E::NC + c];
+                        if (!first) { const uint4 o = E::ld(A, c); t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w; }
+                        E::st(A, c, t);
+                    }
+                    if (++since_norm == 6) {
+                        since_norm = 0;
+                        uint32_t cy = 0;
+#pragma unroll 1
+                        for (int c = 0; c < E::NC; ++c) {
+                            uint4 t = E::ld(A, c);
+                            t.x += cy; cy = t.x >> RB; t.x &= RMASK;
+                            t.y += cy; cy = t.y >> RB; t.y &= RMASK;
+                            t.z += cy; cy = t.z >> RB; t.z &= RMASK;
+                            t.w += cy; cy = t.w >> RB; t.w &= RMASK;
+                            E::st(A, c, t);
+                        }                                       // (the sum stays far below 2^(29 NL): cy == 0 at the top)
+                    }
+                };
+                // the idle digit of the pair rests in LDS buffer B: x goes there, y comes back
+                auto park = [&](const int32_t (&x)[NL], int32_t (&y)[NL]) {
+#pragma unroll
+                    for (int c = 0; c < E::NC; ++c) {
+                        const uint4 t = E::ld(B, c);
+                        y[4 * c] = (int32_t)t.x; y[4 * c + 1] = (int32_t)t.y; y[4 * c + 2] = (int32_t)t.z; y[4 * c + 3] = (int32_t)t.w;
+                        E::st(B, c, make_uint4((uint32_t)x[4 * c], (uint32_t)x[4 * c + 1], (uint32_t)x[4 * c + 2], (uint32_t)x[4 * c + 3]));
+                    }
+                };
+                int32_t a[NL], b[NL];
+                uint32_t ub_[NL];
+                uint4 pre[HC];                                // the half entry the next step takes, requested one step ahead
+                wave_lds_fence();
+                {
+                    const uint4* ent = entry(0);
+                    add_t(ent, true);
+                    int32_t cy = 0;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        uint4 raw[HC];
+                        uint32_t u[NL / 2];
+                        int32_t r[NL / 2];
+                        fetch_half(ent, h, raw);
+                        half_limbs(raw, u);
+                        E::balance_half(u, h, cy, r);
+#pragma unroll
+                        for (int j = 0; j < NL / 2; ++j) a[h * (NL / 2) + j] = r[j];
+                    }
+#pragma unroll 1
+                    for (int c = 0; c < E::NC; ++c) E::st(B, c, make_uint4(0u, 0u, 0u, 0u));
+                }
+                // pre: the half of an entry the NEXT step takes, requested one step ahead (the first half of the next window's
+                // entry before the product's last step) — never beyond the last window
+                const uint4* ent = nullptr;
+                if (P.fb_windows > 1) {
+                    ent = entry(1);
+                    fetch_half(ent, 0, pre);
+                }
+#pragma unroll 1
+                for (int jw = 1; jw < P.fb_windows; ++jw) {
+                    add_t(ent, false);
+                    const uint4* cur = ent;
+                    int32_t cy = 0;
+                    E::mul_kara2_c0_bal(a, [&](int step, int32_t (&ch)[NL / 2]) {
+                        uint32_t u[NL / 2];
+                        half_limbs(pre, u);
+                        E::balance_half(u, step & 1, cy, ch);
+                        if (step < 3) {
+                            fetch_half(cur, (step + 1) & 1, pre);
+                        } else if (jw + 1 < P.fb_windows) {
+                            ent = entry(jw + 1);
+                            fetch_half(ent, 0, pre);
+                        }
+                    }, park, nb, ndp, n0inv);
+                }
+                // the exponent sum back into registers, then the pair as the row-wise exit takes it, the same residue modulo n^2:
+                // a + b n = (a + n) + (b - 1 + n) n - n^2, both in (0.49 n - 1, 1.51 n) (a single window: the entry itself plus n)
+                wave_lds_fence();
+#pragma unroll
+                for (int c = 0; c < E::NC; ++c) {
+                    const uint4 t = E::ld(A, c);
+                    tsum[4 * c] = t.x; tsum[4 * c + 1] = t.y; tsum[4 * c + 2] = t.z; tsum[4 * c + 3] = t.w;
+                }
+                E::load_digit(B, ub_);
+#pragma unroll
+                for (int j = 0; j < NL; ++j) b[j] = (int32_t)ub_[j];
+                uint32_t ua[NL], ub[NL];
+                E::from_balanced_plus_p(a, nb, 0, ua);
+                E::from_balanced_plus_p(b, nb, 1, ub);
+                wave_lds_fence();
+                E::store_digit(A, ua);
+                E::store_digit(B, ub);
+                wave_lds_fence();
+            } else {
             if constexpr (GFORM) {
 #pragma unroll
                 for (int j = 0; j < NL; ++j) tsum[j] = 0;
@@ -518,6 +645,7 @@ k_encrypt_padic(EncPadicParams P, const uint32_t* __restrict__ m, const uint32_t
                     };
                     E::mul_fused(A, B, from_ent(0), from_ent(1), nm, nm1, n0inv);
                 }
+            }
             }
             // times the plain digit pair (1, m) of 1 + m n  => plain digit pair of the ciphertext
             {

@@ -1350,6 +1350,175 @@ struct Padic {
         }
     }
 
+    // ---- (a, b) <- (a, b) * (c, 0) beyond 36 limbs: the balanced columns in TWO half-width steps --------------------------------
+    // kara_pass_bal keeps a whole column in one signed cell, which holds for NL <= 36 only.  With HL = NL / 2, X = 2^(29 HL),
+    // R = X^2 and c = c0 + c1 X the same Montgomery product is reduced by X twice:
+    //        w:  T = (a c0 + q0 n) / X            w = (T + a c1 + q1 n) / X
+    //        v:  S = (b c0 - q0 + q0' n) / X      v = (S + b c1 - q1 + q1' n) / X
+    // m = q0 + X q1 and m' = q0' + X q1' are the balanced quotients of the one-step rule (they are unique), so w and v are
+    // those of kara_pass_bal's rule at R; the invariant |w|, |v| < 0.51 n carries over.
+    // One step (kara2_step_bal) is NL + HL - 1 columns.  A column has at most HL product terms (c_h has HL limbs), HL quotient
+    // terms (q_h has HL digits), one carried-in digit, one digit of the first quotient and the carry:
+    // 36 (2^56 + 2^56) + 2^32 + 2^28 + 2^35 < 2^62.2 at NL = 72, inside one signed cell.
+    // Karatsuba.  The step's four products are HL x HL: x_lo c_h and q_h n_lo enter at column 0, x_hi c_h and q_h n_hi at
+    // column HL, each split at H = HL / 2 as in kara_pass_bal:  X_j = V_j + V_(j-H) - D_(j-H) with V_j = P0_j + P2_(j-H), and
+    // U_j, E_j for the quotient products.  All four share H, so ONE stored sum serves them all,
+    //        S_k = V^lo_k + V^hi_(k-HL) + U^lo_k + U^hi_(k-HL),        d_k = S_k + S_(k-H) - (D, E terms) + tin_k - qin_k + carry,
+    // H live sums, needed modulo 2^64 only.  q_h n_lo is the quotient product whose digits appear one per column: for
+    // H <= k < HL the column is formed without q[k] (its -E term takes q[k-H] alone), then q[k] n[0] is added (kara_pass_bal:
+    // KRED).  q_h is complete from column HL on, so q_h n_hi is a plain product.  3 H^2 multiply-adds per product and H more for
+    // the collapse: 3 906 per step at NL = 72, 15 624 per (a, b) * (c, 0) against 4 NL^2 = 20 736 (executed: 4 032 and 16 128,
+    // see the digits taken twice below and the run-time scalars of the one body).
+    // ndp: the half differences of the modulus, ndp[l] = nm[H + l] - nm[l] and ndp[H + l] = nm[HL + H + l] - nm[HL + l].
+    // Cells: tools/kara_model.py (kara2_step_bal).
+#ifndef PAI_KARA2_SCHED_EVERY
+#define PAI_KARA2_SCHED_EVERY 4       // columns between scheduling fences of kara2_step_bal (0: none)
+#endif
+    // t is the carried-in vector on entry (zero in the first step of a stream) and the step's result on return: digit j is
+    // written at column HL + j, after t[j] was read at column j.  qsel = -1 subtracts the first quotient's digits qin (the v
+    // stream), 0 leaves them out: ONE body serves all four steps of a product, which keeps the loop inside the instruction cache.
+    PAI_DEV static void kara2_step_bal(int32_t (&t)[NL], int32_t (&q)[NL / 2], const int32_t (&x)[NL], const int32_t (&ch)[NL / 2],
+                                       const int32_t (&qin)[NL / 2], int32_t qsel, const int32_t* __restrict__ nm,
+                                       const int32_t* __restrict__ ndp, uint32_t n0inv) {
+        static_assert(NL % 4 == 0 && NL <= 72, "two splits; (NL / 2) (2^57) + 2^36 < 2^63");
+        constexpr int HL = NL / 2, H = NL / 4, NP = 2 * H - 1, NU = HL + H + NP, NK = NL + HL - 1;
+        int32_t nx[HL], dy[H], dm[H];                     // nx: x1 - x0 of either half of x; dy = ch0 - ch1; dm = q0 - q1
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            nx[i] = x[H + i] - x[i];
+            nx[H + i] = x[HL + H + i] - x[HL + i];
+            dy[i] = ch[i] - ch[H + i];
+        }
+        const int32_t one = (int32_t)(n0inv & 1u);        // a run-time 1 (n0inv is odd): the carried-in digit is ONE multiply-add (see kara_pass_bal)
+        uint64_t ss[NU];
+        uint64_t carry = 0;
+        // the index range of i in sum_(i + l = j), 0 <= i, l < H
+        auto lo_of = [](int j) { return j < H ? 0 : j - H + 1; };
+        auto hi_of = [](int j) { return j < H ? j : H - 1; };
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int kh = k - HL;                        // column of the products that enter at HL
+            uint64_t s = 0;
+            // V: x_lo c_h at k, x_hi c_h at kh
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                const int c = o ? kh : k, xo = o ? HL : 0;
+                if (c >= 0 && c < NP) {
+#pragma unroll
+                    for (int i = lo_of(c); i <= hi_of(c); ++i) s += smul(x[xo + i], ch[c - i]);
+                }
+                if (c >= H && c - H < NP) {
+                    const int j = c - H;
+#pragma unroll
+                    for (int i = lo_of(j); i <= hi_of(j); ++i) s += smul(x[xo + H + i], ch[H + j - i]);
+                }
+            }
+            // U: q_h n_hi at kh (every digit known) ...
+            if (kh >= 0 && kh < NP) {
+#pragma unroll
+                for (int i = lo_of(kh); i <= hi_of(kh); ++i) s += smul(q[i], nm[HL + kh - i]);
+            }
+            if (kh >= H && kh - H < NP) {
+                const int j = kh - H;
+#pragma unroll
+                for (int i = lo_of(j); i <= hi_of(j); ++i) s += smul(q[H + i], nm[HL + H + j - i]);
+            }
+            // ... and q_h n_lo at k: the digits below k, the newest (q[k - 1]) last; the column's own digit follows below
+            if (k < NP) {
+#pragma unroll
+                for (int i = lo_of(k); i <= hi_of(k); ++i)
+                    if (i < k) s += smul(q[i], nm[k - i]);
+            }
+            if (k >= H && k - H < NP) {
+                const int j = k - H;
+#pragma unroll
+                for (int i = lo_of(j); i <= hi_of(j); ++i)
+                    if (!(i == j && k < HL)) s += smul(q[H + i], nm[H + j - i]);
+            }
+            // what does not wait for the previous column: S_(k-H), -D, -E, the carried-in digit, the first quotient's digit
+            uint64_t e = k >= H && k - H < NU ? ss[k - H] : 0;
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                const int j = (o ? kh : k) - H;
+                if (j >= 0 && j < NP) {
+#pragma unroll
+                    for (int i = lo_of(j); i <= hi_of(j); ++i) e += smul(nx[o * H + i], dy[j - i]);
+#pragma unroll
+                    for (int i = lo_of(j); i <= hi_of(j); ++i) {
+                        if (o == 0 && i == j && k < HL) e += smul(q[i], ndp[0]);
+                        else e += smul(dm[i], ndp[o * H + j - i]);
+                    }
+                }
+            }
+            if (k < NL) e += smul(t[k], one);
+            if (k < HL) e += smul(qin[k], qsel);
+            uint64_t d = e + s + carry;
+            if (k < HL) {
+                q[k] = sfield((uint32_t)d * n0inv);
+                d += smul(q[k], nm[0]);
+                if (k < H) {
+                    s += smul(q[k], nm[0]);
+                } else {
+                    s += smul(q[k], nm[H]);
+                    dm[k - H] = q[k - H] - q[k];
+                }
+            } else {
+                t[k - HL] = sfield((uint32_t)d);
+            }
+            if (k < NU) ss[k] = s;
+            carry = (uint64_t)((int64_t)(k < HL ? d : d + (1ull << (RB - 1))) >> RB);
+            // the chains of later columns wait for nothing but registers: without a fence the scheduler starts them far ahead
+            // and the block spills (profiles/r19/variants.jsonl)
+            if (PAI_KARA2_SCHED_EVERY > 0 && k % PAI_KARA2_SCHED_EVERY == PAI_KARA2_SCHED_EVERY - 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        t[NL - 1] = (int32_t)carry;
+    }
+    // (a, b) <- (a, b) * (c, 0), c = (c0, c1) in balanced digits (balance_half): the four steps in the order w, w, v, v (the
+    // quotient digits of w stay for v, one of T / S is live at a time) as ONE rolled loop around one inlined step;
+    // csrc(step, ch), step = 0 .. 3, fills half (step & 1) of c.  Only one digit of the pair is in use at a time: x is a on
+    // entry with b parked, and park(y, x) parks y and fetches the parked digit into x (the kernel's LDS digit buffer), so
+    // the idle digit costs no registers; on return x is the new a and the new b is parked.
+    template <class CSrc, class Park>
+    PAI_DEV static void mul_kara2_c0_bal(int32_t (&x)[NL], CSrc&& csrc, Park&& park, const int32_t* __restrict__ nm,
+                                         const int32_t* __restrict__ ndp, uint32_t n0inv) {
+        int32_t ch[NL / 2], q[NL / 2], qin[NL / 2], qa[NL / 2], qb[NL / 2], t[NL];
+#pragma unroll
+        for (int j = 0; j < NL / 2; ++j) qin[j] = qa[j] = qb[j] = 0;
+#pragma unroll 1
+        for (int step = 0; step < 4; ++step) {
+            csrc(step, ch);
+            if ((step & 1) == 0) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) t[j] = 0;
+            }
+            if (step >= 2) {
+#pragma unroll
+                for (int j = 0; j < NL / 2; ++j) qin[j] = step == 2 ? qa[j] : qb[j];
+            }
+            kara2_step_bal(t, q, x, ch, qin, step >= 2 ? -1 : 0, nm, ndp, n0inv);
+            if (step < 2) {
+#pragma unroll
+                for (int j = 0; j < NL / 2; ++j) {
+                    if (step == 0) qa[j] = q[j];
+                    else qb[j] = q[j];
+                }
+            }
+            if (step & 1) park(t, x);
+        }
+    }
+    // half h of an entry's unsigned limbs -> balanced digits; cy is the carry between the halves (0 into half 0), the top
+    // limb of half 1 keeps the rest
+    PAI_DEV static void balance_half(const uint32_t (&u)[NL / 2], int h, int32_t& cy, int32_t (&r)[NL / 2]) {
+        if (h == 0) cy = 0;
+#pragma unroll
+        for (int j = 0; j < NL / 2; ++j) {
+            const int32_t t = (int32_t)u[j] + cy;
+            r[j] = sfield((uint32_t)t);
+            cy = (t + (1 << (RB - 1))) >> RB;
+        }
+        r[NL / 2 - 1] += h == 1 ? cy << RB : 0;
+    }
+
     // (A, B) <- (A, B) * (C, D), the second operand's digits supplied per row block
     template <class CSrc, class DSrc>
     PAI_DEV static void mul(uint4* A, uint4* B, MBuf M, CSrc&& csrc, DSrc&& dsrc, const uint32_t* __restrict__ nm,

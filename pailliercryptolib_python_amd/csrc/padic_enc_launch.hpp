@@ -7,6 +7,10 @@
 
 namespace pai {
 
+// padic_enc_kara_kernels.hip
+void launch_encrypt_padic_kara72(hipStream_t s, int grid, const EncPadicParams& P, const uint32_t* m, const uint32_t* r,
+                                 const uint32_t* ct_in, uint32_t* ct_out, int n, int mode);
+
 template <int NL, int U>
 struct EncLaunch {
     static constexpr int BYTES2 = 2 * NL * BLOCK_THREADS * 4 + 2 * NL * 4;      // digit pair per lane + modulus copies
@@ -28,6 +32,12 @@ struct EncLaunch {
             launch(kernel, dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, m, r, ct_in, ct_out, n, mode);
         };
         const bool gf = PAI_ENC_GFORM_OK && P.fb_gform != 0;
+        if constexpr (NL == 72) {
+            if (gf && mode == 1 && P.enc_kara != 0) {
+                launch_encrypt_padic_kara72(s, grid, P, m, r, ct_in, ct_out, n, mode);
+                return;
+            }
+        }
         if (mode == 2) {
             if (gf) go(k_encrypt_padic<NL, U, true, PAI_ENC_GFORM_OK>);
             else go(k_encrypt_padic<NL, U, true, false>);

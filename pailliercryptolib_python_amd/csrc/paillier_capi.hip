@@ -409,6 +409,8 @@ struct ScopedKernelTimer {
 //                                  padic_one_sum (36-limb decrypt: two stored sums per column, V_k of the product stream and U_k of the
 //                                  quotient stream, kernel mode PADIC_LDS_KMRB, instead of the one sum S_k of PADIC_LDS_KMRBS),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
+//                                  enc_kara (72-limb DJN encryption on a g-factored table: the row-wise product kernel instead of the
+//                                  Karatsuba-column kernel k_encrypt_padic<72, 12, false, true, true>),
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch),
 //                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,

@@ -19,6 +19,8 @@ value and records the largest one, and it asserts that
   - for a product: the summed half products of a d + b c fit 64 bits, their signed difference part fits int64, the middle
     part is non-negative and enters through a 128-bit cell, and w, v are those of the row-wise product rule.
 The balanced-digit form (kara_pass_bal, one signed 64-bit cell per column) has its own model below: kara_pass_bal.
+The product (a, b) * (c, 0) beyond 36 limbs in two half-width steps (kara2_step_bal, mul_kara2_c0_bal: the 72-limb encryption
+kernel) follows it: kara2_step_bal, in wrapping 64-bit cells, every finished column asserted to be the exact schoolbook column.
 Run: python tools/kara_model.py [rounds]
 """
 import random
@@ -813,6 +815,202 @@ def run_bal(rounds=1, seed=2):
     return st
 
 
+# ---- (a, b) * (c, 0) beyond 36 limbs in two half-width steps (csrc/mont_padic.hpp: kara2_step_bal, mul_kara2_c0_bal) --------
+# X = 2^(29 HL), HL = NL / 2, R = X^2, c = c0 + c1 X:
+#     w:  T = (a c0 + q0 n) / X          w = (T + a c1 + q1 n) / X
+#     v:  S = (b c0 - q0 + q0' n) / X    v = (S + b c1 - q1 + q1' n) / X
+# One step is NL + HL - 1 columns; its four HL x HL products (x_lo c_h, q_h n_lo at column 0; x_hi c_h, q_h n_hi at column HL)
+# are split at H = HL / 2 and share ONE stored sum S_k per column, kept in a 64-bit cell that WRAPS.  The model asserts that every
+# finished column, read as a signed 64-bit integer, is the exact schoolbook column of the step, and records the largest one.
+class Kara2Stats:
+    def __init__(self):
+        self.max_d = 0                        # largest |finished column|
+        self.max_c = 0                        # largest |carry|
+        self.at_d = None                      # (second, has_tin, column) of the largest column
+        self.macs = 0                         # multiply-adds of the last step
+        self.q_ext = set()                    # extreme quotient digits met: -2^28, 2^28 - 1
+
+
+def _s64(v):
+    v &= M64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def kara2_step_bal(x, ch, tin, qin, nm, n0inv, st, second, has_tin):
+    """One step of kara2_step_bal on signed limb lists: (out limbs, quotient digits).  second: the v stream (qsel = -1, qin the
+    first quotient's digits); has_tin: the second step of a stream (tin the first step's result, else zero)."""
+    NL = len(x)
+    assert NL % 4 == 0 and NL <= 72 and len(ch) == NL // 2 and len(nm) == NL
+    HL, H = NL // 2, NL // 4
+    NP = 2 * H - 1
+    NU, NK = HL + H + NP, NL + HL - 1
+    i32 = lambda v: -(1 << 31) <= v < (1 << 31)
+    nx = [x[H + i] - x[i] for i in range(H)] + [x[HL + H + i] - x[HL + i] for i in range(H)]
+    dy = [ch[i] - ch[H + i] for i in range(H)]
+    ndp = [nm[H + l] - nm[l] for l in range(H)] + [nm[HL + H + l] - nm[HL + l] for l in range(H)]
+    assert all(i32(v) for v in nx + dy + ndp)
+    dm = [None] * H
+    q = [None] * HL
+    out = [None] * NL
+    ss = [None] * NU
+    carry = 0
+    macs = 0
+    lo_of = lambda j: 0 if j < H else j - H + 1
+    hi_of = lambda j: j if j < H else H - 1
+
+    def smul(a, b):
+        nonlocal macs
+        assert i32(a) and i32(b)
+        macs += 1
+        return a * b
+
+    for k in range(NK):
+        kh = k - HL
+        s = 0
+        for o in (0, 1):
+            c, xo = (kh, HL) if o else (k, 0)
+            if 0 <= c < NP:
+                for i in range(lo_of(c), hi_of(c) + 1):
+                    s += smul(x[xo + i], ch[c - i])
+            if c >= H and c - H < NP:
+                j = c - H
+                for i in range(lo_of(j), hi_of(j) + 1):
+                    s += smul(x[xo + H + i], ch[H + j - i])
+        if 0 <= kh < NP:
+            for i in range(lo_of(kh), hi_of(kh) + 1):
+                s += smul(q[i], nm[HL + kh - i])
+        if kh >= H and kh - H < NP:
+            j = kh - H
+            for i in range(lo_of(j), hi_of(j) + 1):
+                s += smul(q[H + i], nm[HL + H + j - i])
+        if k < NP:
+            for i in range(lo_of(k), hi_of(k) + 1):
+                if i < k:
+                    s += smul(q[i], nm[k - i])
+        if k >= H and k - H < NP:
+            j = k - H
+            for i in range(lo_of(j), hi_of(j) + 1):
+                if not (i == j and k < HL):
+                    s += smul(q[H + i], nm[H + j - i])
+        s &= M64
+        e = ss[k - H] if k >= H else 0
+        for o in (0, 1):
+            j = (kh if o else k) - H
+            if 0 <= j < NP:
+                for i in range(lo_of(j), hi_of(j) + 1):
+                    e += smul(nx[o * H + i], dy[j - i])
+                for i in range(lo_of(j), hi_of(j) + 1):
+                    if o == 0 and i == j and k < HL:
+                        e += smul(q[i], ndp[0])
+                    else:
+                        e += smul(dm[i], ndp[o * H + j - i])
+        # one body serves all four steps: the carried-in digit (zero in the first step of a stream) is one multiply-add by a
+        # run-time 1, the first quotient's digit one by qsel = -1 (v stream) or 0 (w stream)
+        if k < NL:
+            e += smul(tin[k] if has_tin else 0, 1)
+        if k < HL:
+            e += smul(qin[k] if second else 0, -1 if second else 0)
+        d = (e + s + carry) & M64
+        # the exact schoolbook column of the step without the column's own digit
+        col = sum(x[i] * ch[k - i] for i in range(NL) if 0 <= k - i < HL)
+        col += sum(q[i] * nm[k - i] for i in range(min(k, HL)) if 0 <= k - i < NL)
+        col += (tin[k] if has_tin and k < NL else 0) - (qin[k] if second and k < HL else 0) + _s64(carry)
+        assert _s64(d) == col, ("column", k)
+        if k < HL:
+            q[k] = sfield(d * n0inv)
+            if q[k] in (-HB, HB - 1):
+                st.q_ext.add(q[k])
+            d = (d + smul(q[k], nm[0])) & M64
+            col += q[k] * nm[0]
+            assert _s64(d) == col and col % B == 0
+            if k < H:
+                s = (s + smul(q[k], nm[0])) & M64
+            else:
+                s = (s + smul(q[k], nm[H])) & M64
+                dm[k - H] = q[k - H] - q[k]
+                assert i32(dm[k - H])
+        else:
+            out[k - HL] = sfield(d)
+        if abs(col) > st.max_d:
+            st.max_d, st.at_d = abs(col), (second, has_tin, k)
+        assert abs(col) < 1 << 63
+        if k < NU:
+            ss[k] = s
+        carry = (_s64(d) if k < HL else _s64(d) + HB) >> RB
+        st.max_c = max(st.max_c, abs(carry))
+        carry &= M64
+    out[NL - 1] = _s64(carry)
+    assert i32(out[NL - 1])
+    st.macs = macs
+    return out, q
+
+
+def balance_halves(u):
+    """Padic::balance_half on both halves of an entry's unsigned limbs: the balanced digits of the same integer."""
+    NL = len(u)
+    r, cy = [], 0
+    for j in range(NL):
+        t = u[j] + cy
+        assert -(1 << 31) <= t + HB < (1 << 31)
+        r.append(sfield(t))
+        cy = (t + HB) >> RB
+    r[NL - 1] += cy << RB
+    assert -(1 << 31) <= r[-1] < (1 << 31)
+    return r
+
+
+def mul_kara2_c0_bal(al, bl, cl, n, st, check=True):
+    """(a, b) * (c, 0) -> (w, v, m digits, m' digits) by mul_kara2_c0_bal on balanced limb lists; with `check` the one-step
+    rule in CPython: w R = a c + m n, v R = b c - m + m' n, the same balanced quotients, and the product rule modulo n^2."""
+    NL = len(al)
+    HL = NL // 2
+    R = 1 << (RB * NL)
+    nm, n0inv = _bal_ctx(n, NL)
+    assert value(nm) == n
+    c0, c1 = cl[:HL], cl[HL:]
+    t, q0 = kara2_step_bal(al, c0, None, None, nm, n0inv, st, False, False)
+    w, q1 = kara2_step_bal(al, c1, t, None, nm, n0inv, st, False, True)
+    s, q2 = kara2_step_bal(bl, c0, None, q0, nm, n0inv, st, True, False)
+    v, q3 = kara2_step_bal(bl, c1, s, q1, nm, n0inv, st, True, True)
+    m, m2 = q0 + q1, q2 + q3
+    if check:
+        a, b, c = value(al), value(bl), value(cl)
+        W, M, V, M2 = value(w), value(m), value(v), value(m2)
+        Mref = one_step_quotient(a * c, n, NL)
+        assert M == Mref and W * R == a * c + M * n
+        M2ref = one_step_quotient(b * c - M, n, NL)
+        assert M2 == M2ref and V * R == b * c - M + M2 * n
+        n2 = n * n
+        assert (W + V * n - (a + b * n) * c * pow(R, -1, n2)) % n2 == 0
+    return w, v, m, m2
+
+
+def one_step_quotient(z, n, NL):
+    """The balanced quotient of the one-step rule: m == -z / n (mod R) with every digit in [-2^28, 2^28)."""
+    R = 1 << (RB * NL)
+    m = (-z * pow(n, -1, R)) % R
+    digs = []
+    for _ in range(NL):
+        r = sfield(m)
+        digs.append(r)
+        m = (m - r) >> RB
+    return value(digs)
+
+
+def run_kara2(rounds=1, seed=3, NL=72, bits=2048):
+    rng = random.Random(seed)
+    st = Kara2Stats()
+    for _ in range(rounds):
+        n = random_prime(bits // 2, rng) * random_prime(bits - bits // 2, rng)
+        lo, hi = [-HB] * NL, [HB - 1] * NL
+        cs = [lo, hi, bal_limbs(51 * n // 100, NL), bal_limbs(-(51 * n // 100), NL), bal_limbs(0, NL)]
+        cs += [bal_limbs(rng.randrange(-n // 2, n // 2), NL) for _ in range(2)]
+        for i, a in enumerate(cs):
+            b, c = cs[(i + 1) % len(cs)], cs[(i + 3) % len(cs)]
+            mul_kara2_c0_bal(a, b, c, n, st)
+    return st
+
+
 def random_prime(bits, rng):
     while True:
         c = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
@@ -871,5 +1069,8 @@ if __name__ == "__main__":
     bst = run_bal(rounds)
     print({"bal_max_d_log2": bst.max_d.bit_length(), "bal_max_v_log2": bst.max_v.bit_length(), "bal_max_u_log2": bst.max_u.bit_length(),
            "bal_max_e_log2": bst.max_e.bit_length(), "bal_red_macs": bst.red_macs})
+    k2 = run_kara2(rounds)
+    print({"kara2_max_col_log2": k2.max_d.bit_length(), "kara2_at": k2.at_d, "kara2_max_carry_log2": k2.max_c.bit_length(),
+           "kara2_macs_last_step": k2.macs})
     print({"max_col_log2": s.max_col.bit_length(), "max_cc_log2": s.max_cc.bit_length(),
            "max_d_log2": s.max_d.bit_length(), "max_running_log2": s.max_run.bit_length(), "max_mid_cell_log2": s.max_e.bit_length()})
