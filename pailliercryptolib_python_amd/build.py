@@ -38,6 +38,7 @@ SOURCES = [
     "padic_dec_kmr_kernels.hip",
     "padic_dec_kmrb_kernels.hip",
     "padic_dec_kmrbs_kernels.hip",
+    "padic_dec_kmrbt_kernels.hip",
     "padic_enc_kernels.hip",
     "padic_enc_kara_kernels.hip",
     "padic_enc36_kernels.hip",

@@ -459,7 +459,9 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
             // otherwise; the other limb counts row-wise.  The path name of the first two register-resident kernels is the same.)
             const char* padic_path = sk->padic_nl != 36 ? "padic" : (!sqr_kara ? "padic_rowwise" : (mul_kara ? "padic_kara_mul" : "padic_kara"));
             ScopedKernelTimer t("k_dec_a", s, sk->padic_nl ? padic_path : (sk->wide_nl ? "wide" : "lane_group"));
-            if (sk->padic_nl == 36 && sqr_kara && mul_kara) t.mode = one_sum ? "kmrb" : (bal_kara ? "kmrb2s" : (red_kara ? "kmr" : "km"));
+            const bool stage = one_sum && !knob_disabled("padic_stage");   // PAI_DISABLE=padic_stage: the right operand of a product loaded into registers at its head instead of staged in LDS ahead of the squarings (the PADIC_LDS_KMRBS kernel)
+            if (sk->padic_nl == 36 && sqr_kara && mul_kara)
+                t.mode = stage ? "kmrb" : (one_sum ? "kmrbh" : (bal_kara ? "kmrb2s" : (red_kara ? "kmr" : "km")));
             if (sk->padic_nl) {
                 DecPadicParams Q;
                 for (int w = 0; w < 2; ++w) {
@@ -478,7 +480,7 @@ int pai_decrypt(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_m, 
                 Q.mul_kara = mul_kara;
                 Q.red_kara = red_kara;
                 Q.bal_kara = bal_kara;
-                Q.one_sum = one_sum;
+                Q.one_sum = stage ? 2 : (one_sum ? 1 : 0);   // 2: MODE PADIC_LDS_KMRBT (the structure keeps its size)
                 if (!launch_dec_a_padic(sk->padic_nl, s, gridx, Q, d_ct, sk->ubuf.as<uint32_t>(), (int)N, sk->table.as<uint32_t>()))
                     throw PaiError(PAI_E_INTERNAL, "no p-adic kernel for this limb count");
             } else if (sk->wide_nl) {

@@ -23,7 +23,8 @@ struct DecPadicParams {
     int mul_kara;                // ... and the products too, digits kept in registers between operations (MODE PADIC_LDS_KM)
     int red_kara;                // ... and the quotient products of the reductions (MODE PADIC_LDS_KMR); needs mul_kara
     int16_t bal_kara;            // ... on balanced digits, one carry stream per column (MODE PADIC_LDS_KMRB); needs red_kara
-    int16_t one_sum;             // ... with one stored sum per column for both streams (MODE PADIC_LDS_KMRBS); needs bal_kara
+    int16_t one_sum;             // ... with one stored sum per column for both streams (1: MODE PADIC_LDS_KMRBS; 2: MODE
+                                 // PADIC_LDS_KMRBT, the right operand of a product staged in LDS on top); needs bal_kara
                                  // (two halves of one word: the structure is a kernel argument and keeps its size, so the
                                  // kernels of the other modes keep their code objects)
 };
@@ -120,8 +121,24 @@ constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 // MODE PADIC_LDS_KMRBS: PADIC_LDS_KMRB with ONE stored sum per column, S_k = [2] V_k + U_k, for the product stream and the quotient
 //                   stream together in both passes of a squaring and the first pass of a product (mont_padic.hpp: kara_pass_bal,
 //                   ONES; PADIC_KMRBS_RED).  Same digits, quotient digits and carries, same LDS, same table.
+// MODE PADIC_LDS_KMRBT: PADIC_LDS_KMRBS with the right operand of a product STAGED in LDS.  At the top of a step, before its
+//                   squarings, the wave copies tbl(idx) (18 x 1 KiB) from HBM straight into its own A and B digit buffers, idle
+//                   between entry and exit, by direct-to-LDS loads that touch no register; the product waits for them (vmcnt)
+//                   and reads c and d from LDS.  No barrier: a wave reads what it loaded itself.  The staged index is kept per
+//                   tile (the entry and the exit write A and B), so base^2 is fetched once for the whole table build, and all
+//                   staged loads have landed before the exit stores into A and B.  Same digits, same LDS size, same table.
+//                   The compiler does not order an LDS read behind a direct-to-LDS load in flight: the waits are explicit.
+//                   (PAI_KMRBT_PARTS & 2, not shipped: the second pass of a product in the one-sum form with Karatsuba quotient
+//                   products on top, PADIC_KMRBT_RED.)
+#ifndef PAI_KMRBT_PARTS
+#define PAI_KMRBT_PARTS 1             // bit 0: the staged operand (shipped), bit 1: the second pass of a product in the one-sum form
+                                      // (measured alone and on top of the staged operand, not shipped: profiles/r20/README.md)
+#endif
+#ifndef PAI_KMRBT_REREAD
+#define PAI_KMRBT_REREAD 0            // 1: the product reads c from LDS again for its second pass (profiles/r20/README.md)
+#endif
 constexpr int PADIC_LDS_M = 0, PADIC_WBUF = 1, PADIC_LDS_K = 2, PADIC_LDS_KM = 3, PADIC_LDS_KMR = 4, PADIC_LDS_KMRB = 5,
-              PADIC_LDS_KMRBS = 6;
+              PADIC_LDS_KMRBS = 6, PADIC_LDS_KMRBT = 7;
 constexpr bool padic_reg_mode(int mode) { return mode == PADIC_LDS_KM || mode == PADIC_LDS_KMR; }
 template <int NL, int U, int WB, int MODE>
 __global__ void __launch_bounds__(BLOCK_THREADS, 1)
@@ -182,8 +199,13 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         const uint32_t* row = ct + (size_t)es * P.ct_words;
         // ---- digit form of ct:  sum_i  (c_i, 0) * digits(R^(i+2) mod s^2) -----------------------------
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
-        if constexpr (MODE == PADIC_LDS_KMRB || MODE == PADIC_LDS_KMRBS) {
-            constexpr int BRED = MODE == PADIC_LDS_KMRBS ? E::PADIC_KMRBS_RED : E::PADIC_KMRB_RED;
+        if constexpr (MODE == PADIC_LDS_KMRB || MODE == PADIC_LDS_KMRBS || MODE == PADIC_LDS_KMRBT) {
+            constexpr bool STAGE = MODE == PADIC_LDS_KMRBT && (PAI_KMRBT_PARTS & 1) != 0;
+            constexpr int BRED = MODE == PADIC_LDS_KMRBT ? ((PAI_KMRBT_PARTS & 2) ? E::PADIC_KMRBT_RED : E::PADIC_KMRBS_RED)
+                                 : MODE == PADIC_LDS_KMRBS ? E::PADIC_KMRBS_RED : E::PADIC_KMRB_RED;
+            // STAGE: the table entry this wave's A and B hold as a product's right operand (wave-uniform), none at the top of a
+            // tile: padic_to_digit_form above has just written both buffers
+            [[maybe_unused]] int staged = -1;
             // ---- the loop of PADIC_LDS_KM / PADIC_LDS_KMR below (same steps, same table slots) on balanced digits --------
             const int NT = P.tbl_entries;
             int32_t nb[NL];                               // balanced modulus limbs: wave-uniform, formed once from the SGPR copy
@@ -215,10 +237,33 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
                     nsq = op & 0xFF; idx = op >> 8; put_e = -1;
                 }
                 if (t == NT - 1) get_e = i0;
+                if constexpr (STAGE) {
+                    // the product's operand on its way into LDS while the squarings run: lane i's 16 bytes land at base + 16 i,
+                    // the digit buffers' own layout.  A slot this lane stored earlier (put) is read behind that store, as the
+                    // register loads of the other modes are: one wave's vector memory operations stay in order.
+                    if (idx != 0xFF && idx != staged) {
+                        typedef __attribute__((address_space(1))) const void gvoid;
+                        typedef __attribute__((address_space(3))) void lvoid;
+#pragma unroll
+                        for (int c = 0; c < E::NC; ++c) {
+                            __builtin_amdgcn_global_load_lds((gvoid*)&tbl(idx, 0, c), (lvoid*)(A - lane + c * 64), 16, 0, 0);
+                            __builtin_amdgcn_global_load_lds((gvoid*)&tbl(idx, 1, c), (lvoid*)(B - lane + c * 64), 16, 0, 0);
+                        }
+                        staged = idx;
+                    }
+                }
 #pragma unroll 1
                 for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<BRED>(a, b, nb, n0inv);
-                if (idx != 0xFF)
-                    E::template mul_kara_reg_bal<BRED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
+                if (idx != 0xFF) {
+                    if constexpr (STAGE) {
+                        // (in every product: waiting only in the steps that staged loses the gain in this build,
+                        // profiles/r20/README.md)
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        E::template mul_kara_lds_bal<BRED, PAI_KMRBT_REREAD != 0>(a, b, A, B, nb, n0inv);
+                    } else {
+                        E::template mul_kara_reg_bal<BRED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
+                    }
+                }
                 if (put_e >= 0) put(put_e);
                 if (get_e >= 0) {
 #pragma unroll
@@ -234,6 +279,9 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
             uint32_t ua[NL], ub[NL];
             E::from_balanced_plus_p(a, nb, 0, ua);
             E::from_balanced_plus_p(b, nb, 1, ub);
+            // STAGE: every staged load has landed before the exit writes A and B (each was waited for by its product; this
+            // makes it hold whatever the schedule)
+            if constexpr (STAGE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             wave_lds_fence();
             E::store_digit(A, ua);
             E::store_digit(B, ub);

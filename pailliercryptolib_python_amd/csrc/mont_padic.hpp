@@ -1050,7 +1050,7 @@ struct Padic {
         // the compiler emits sign extension, subtract and borrow (three instructions, 36 columns)
         const int32_t neg1 = -(int32_t)(n0inv & 1u);
         uint64_t carry = 0;
-        if constexpr (ONES != 0 && KRED && VF && !SUM) {
+        if constexpr (ONES != 0 && KRED && VF) {
             // ONE stored sum per column.  V_k and U_k are both kept for H columns and both enter column k and column k + H, never
             // apart: S_k = [2] V_k + U_k is all that is needed, and the column is
             //        d_k = S_k + S_(k-H) - [2] D_(k-H) - E_(k-H) - min_k + carry,
@@ -1061,6 +1061,10 @@ struct Padic {
             // same integer as in the two-sum form, so mq, out and carry are bit for bit the same.  ONES == 1: the terms of the
             // newest digit mq[k - 1] go onto s before the column is formed; ONES == 2: onto s and onto the column, one
             // multiply-add more and s off the column's dependency chain.  Cells: tools/kara_model.py (ones).
+            // SUM (the second pass of a product, a d + b c; PADIC_KMRBT_RED only): V_k sums both pairs' products and -D both
+            // pairs' signed products, the latter on e, the chain that does not wait for the carry.  The parts of S_k double
+            // their bounds (|V_k| <= 2 H 2^56) and wrap as before; the finished column is the one of the two-sum form, below
+            // 2^62.76.  Cells: tools/kara_model.py (kara_pass_bal_sum).
             constexpr int NU = H + NP;                    // S_0 .. S_(NU-1)
             uint64_t ss[NU];
 #pragma unroll
@@ -1077,6 +1081,7 @@ struct Padic {
                         else if (!SYM) s += smul(x[i], y[l]);
                         else if (i < l) off += smul(x[i], y[l]);
                         else if (i == l) s += smul(x[i], y[i]);
+                        if (SUM) s += smul(x2[i], y2[l]);
                     }
                 }
                 if (mid) {
@@ -1088,6 +1093,7 @@ struct Padic {
                         else if (!SYM) s += smul(x[H + i], y[H + l]);
                         else if (i < l) off += smul(x[H + i], y[H + l]);
                         else if (i == l) s += smul(x[H + i], y[H + i]);
+                        if (SUM) s += smul(x2[H + i], y2[H + l]);
                     }
                 }
                 if (SYM) s += off << 1;
@@ -1120,6 +1126,7 @@ struct Padic {
                         else if (!SYM) e += smul(nx[i], dy[l]);
                         else if (i < l) nd += smul(nx[i], dy[l]);
                         else if (i == l) e += smul(nx[i], dy[i]);
+                        if (SUM) e += smul(nx2[i], dy2[l]);
                     }
                     if (SYM) e += nd << 1;
 #pragma unroll
@@ -1291,8 +1298,9 @@ struct Padic {
     static constexpr int PADIC_KMRB_RED = PADIC_KMR_RED | KRED_VFS;
     // KRED_ONES = the passes that have both KRED and VF (both of a squaring, the first of a product) keep ONE stored sum per
     // column, S_k = [2] V_k + U_k (kara_pass_bal: ONES); KRED_ONES2 on top = the terms of the newest quotient digit are added
-    // to the sum and to the column separately.  Kernel mode PADIC_LDS_KMRBS.  The second pass of a product keeps its form: with
-    // Karatsuba quotient products and one sum it is shorter by itself, but the squaring in the same loop grows.
+    // to the sum and to the column separately.  Kernel mode PADIC_LDS_KMRBS.  The second pass of a product keeps its form in the
+    // shipped kernels: in the one-sum form with Karatsuba quotient products (PADIC_KMRBT_RED below) it is shorter and gains by
+    // itself, but nothing on top of the staged right operand (profiles/r20/README.md).
     static constexpr int KRED_ONES = 128, KRED_ONES2 = 256;
 #ifndef PAI_KMRBS_NEWEST_TWICE
 #define PAI_KMRBS_NEWEST_TWICE 0      // 1: build the other placement of the newest digit's terms (profiles/r17/README.md)
@@ -1323,7 +1331,39 @@ struct Padic {
             const uint4 t = rsrc(1, ch);
             d[4 * ch] = (int32_t)t.x; d[4 * ch + 1] = (int32_t)t.y; d[4 * ch + 2] = (int32_t)t.z; d[4 * ch + 3] = (int32_t)t.w;
         }
-        kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0>(v, m2, a, d, b, c, m, nm, n0inv);
+        kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, kred(RED, KARA_MUL2) ? ones(RED) : 0>(v, m2, a, d, b, c, m, nm, n0inv);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
+    }
+    // The same product with the right operand (c, d) STAGED in this wave's LDS digit buffers C and D (kernels_padic.hpp:
+    // PADIC_LDS_KMRBT, which loads them from the table ahead of the step's squarings) and, with 1 << KARA_MUL2 in RED, the second
+    // pass in the one-sum form with Karatsuba quotient products as well (PADIC_KMRBT_RED).  The caller has waited for the staged
+    // loads.  REREAD: c is read from LDS again at the head of the second pass instead of being kept in 36 registers across the
+    // first (the empty asm keeps the compiler from merging the two reads).
+    static constexpr int PADIC_KMRBT_RED = PADIC_KMRBS_RED | (1 << KARA_MUL2);
+    PAI_DEV static void load_digit_bal(const uint4* x, int32_t (&r)[NL]) {
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            const uint4 t = ld(x, ch);
+            r[4 * ch] = (int32_t)t.x; r[4 * ch + 1] = (int32_t)t.y; r[4 * ch + 2] = (int32_t)t.z; r[4 * ch + 3] = (int32_t)t.w;
+        }
+    }
+    template <int RED, bool REREAD>
+    PAI_DEV static void mul_kara_lds_bal(int32_t (&a)[NL], int32_t (&b)[NL], const uint4* C, const uint4* D,
+                                         const int32_t* __restrict__ nm, uint32_t n0inv) {
+        constexpr int ONES2ND = kred(RED, KARA_MUL2) ? ones(RED) : 0;
+        int32_t c[NL], d[NL], m[NL], w[NL], m2[NL], v[NL];
+        load_digit_bal(C, c);
+        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0, ones(RED)>(w, m, a, c, a, c, m, nm, n0inv);
+        load_digit_bal(D, d);
+        if constexpr (REREAD) {
+            int32_t c2[NL];
+            asm volatile("" ::: "memory");
+            load_digit_bal(C, c2);
+            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND>(v, m2, a, d, b, c2, m, nm, n0inv);
+        } else {
+            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND>(v, m2, a, d, b, c, m, nm, n0inv);
+        }
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }

@@ -33,12 +33,15 @@ void launch_dec_a_padic_kmr(hipStream_t s, int gridx, const DecPadicParams& P, c
 void launch_dec_a_padic_kmrb(hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table);
 // ... and PADIC_LDS_KMRBS in padic_dec_kmrbs_kernels.hip
 void launch_dec_a_padic_kmrbs(hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table);
+// ... and PADIC_LDS_KMRBT in padic_dec_kmrbt_kernels.hip (one_sum == 2)
+void launch_dec_a_padic_kmrbt(hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct, uint32_t* u_out, int n, uint32_t* table);
 bool launch_dec_a_padic(int nl, hipStream_t s, int gridx, const DecPadicParams& P, const uint32_t* ct,
                         uint32_t* u_out, int n, uint32_t* table) {
     switch (nl) {
         case 24: launch_padic<24, 12, PADIC_LDS_M>(s, gridx, P, ct, u_out, n, table); return true;
         case 36:
-            if (P.sqr_kara && P.mul_kara && P.red_kara && P.bal_kara && P.one_sum) launch_dec_a_padic_kmrbs(s, gridx, P, ct, u_out, n, table);
+            if (P.sqr_kara && P.mul_kara && P.red_kara && P.bal_kara && P.one_sum == 2) launch_dec_a_padic_kmrbt(s, gridx, P, ct, u_out, n, table);
+            else if (P.sqr_kara && P.mul_kara && P.red_kara && P.bal_kara && P.one_sum) launch_dec_a_padic_kmrbs(s, gridx, P, ct, u_out, n, table);
             else if (P.sqr_kara && P.mul_kara && P.red_kara && P.bal_kara) launch_dec_a_padic_kmrb(s, gridx, P, ct, u_out, n, table);
             else if (P.sqr_kara && P.mul_kara && P.red_kara) launch_dec_a_padic_kmr(s, gridx, P, ct, u_out, n, table);
             else if (P.sqr_kara && P.mul_kara) launch_padic<36, 12, PADIC_LDS_KM>(s, gridx, P, ct, u_out, n, table);

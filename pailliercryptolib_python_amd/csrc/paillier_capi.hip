@@ -408,6 +408,9 @@ struct ScopedKernelTimer {
 //                                  instead of balanced digits, PADIC_LDS_KMRB),
 //                                  padic_one_sum (36-limb decrypt: two stored sums per column, V_k of the product stream and U_k of the
 //                                  quotient stream, kernel mode PADIC_LDS_KMRB, instead of the one sum S_k of PADIC_LDS_KMRBS),
+//                                  padic_stage (36-limb decrypt: the right operand of a product loaded from the table into registers at
+//                                  the head of the product, kernel mode PADIC_LDS_KMRBS, profile mode "kmrbh", instead of staged in LDS
+//                                  ahead of the step's squarings, PADIC_LDS_KMRBT),
 //                                  padic_kara_mul (36-limb decrypt products row-wise with the LDS hand-over; squarings stay Karatsuba),
 //                                  enc_kara (72-limb DJN encryption on a g-factored table: the row-wise product kernel instead of the
 //                                  Karatsuba-column kernel k_encrypt_padic<72, 12, false, true, true>),

@@ -785,6 +785,174 @@ def sqr_kara_bal(al, bl, p, st, red=KMRB_RED):
     return w, v
 
 
+# ---- the second pass of a product in the one-sum form (kara_pass_bal<KARA_MUL2, true, true, ONES>; kernel mode PADIC_LDS_KMRBT
+# built with -DPAI_KMRBT_PARTS=3, not the shipped build) ----
+# v = (x y + x2 y2 - min + m' p) / R with Karatsuba quotient products and ONE stored sum per column: S_k = V_k + U_k, where V_k now
+# sums the half products of BOTH pairs (|V_k| <= 2 H 2^56) and -D_(k-H) of both pairs goes onto e, the chain that does not wait for
+# the previous column's carry.  Every cell is a 64-bit word that WRAPS; the finished column, read as a signed 64-bit integer, must
+# be the schoolbook column, the same integer as in the shipped pass (kara_pass_bal(MUL2, vf=True)), so mq, out and the carries are
+# bit for bit the same.  The functions above stay as they are.
+KMRBT_RED = KMRBS_RED | 1 << MUL2     # Padic::PADIC_KMRBT_RED: what kernel mode PADIC_LDS_KMRBT runs with PAI_KMRBT_PARTS & 2
+
+
+def schoolbook_second_pass(x, y, x2, y2, mnin, nm, n0inv):
+    """The rule itself on plain integers, column by column: (out, mq, carries) of v = (x y + x2 y2 - min + m' p) / R."""
+    NL = len(x)
+    mq, out, carries = [0] * NL, [0] * NL, []
+    carry = 0
+    for k in range(2 * NL - 1):
+        lo, hi = max(0, k - NL + 1), min(k, NL - 1)
+        d = sum(x[i] * y[k - i] + x2[i] * y2[k - i] for i in range(lo, hi + 1)) + carry
+        if k < NL:
+            d += sum(mq[i] * nm[k - i] for i in range(k)) - mnin[k]
+            mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+            d += mq[k] * nm[0]
+            assert d % B == 0
+            carry = d >> RB
+        else:
+            d += sum(mq[i] * nm[k - i] for i in range(k - NL + 1, NL))
+            out[k - NL] = sfield(d)
+            carry = (d + HB) >> RB
+        carries.append(carry)
+    out[NL - 1] = carry
+    return out, mq, carries
+
+
+def kara_pass_bal_sum(x, y, x2, y2, mnin, nm, n0inv, st, ones=1):
+    """kara_pass_bal<KARA_MUL2, true, true, ONES> in wrapping 64-bit cells: (out limbs, quotient limbs, carries)."""
+    NL = len(x)
+    H = NL // 2
+    NP = 2 * H - 1
+    assert NL % 2 == 0 and NL <= 36 and ones in (1, 2)
+    i32 = lambda v: -(1 << 31) <= v < (1 << 31)
+    assert all(i32(v) for v in list(x) + list(y) + list(x2) + list(y2) + list(mnin) + list(nm))
+    nx = [x[i + H] - x[i] for i in range(H)]
+    dy = [y[i] - y[i + H] for i in range(H)]
+    nx2 = [x2[i + H] - x2[i] for i in range(H)]
+    dy2 = [y2[i] - y2[i + H] for i in range(H)]
+    ndp = [nm[H + l] - nm[l] for l in range(H)]
+    assert all(i32(v) for v in nx + dy + nx2 + dy2 + ndp), "difference limb leaves int32"
+
+    def smul(a, b):
+        assert i32(a) and i32(b)
+        return a * b
+
+    def rng(j):
+        return (0, j) if j < H else (j - H + 1, H - 1)
+
+    mq, out, carries = [0] * NL, [0] * NL, []
+    dm = [0] * H
+    ss = [0] * (H + NP)
+    carry = 0                                            # a 64-bit word: the arithmetic shift of the finished column
+    macs = 0
+    for k in range(2 * NL - 1):
+        mid = H <= k < H + NP
+        j = k - H
+        s = 0
+        for o, jj, on in ((0, k, k < NP), (H, j, mid)):
+            if not on:
+                continue
+            lo, hi = rng(jj)
+            for i in range(lo, hi + 1):
+                l = jj - i
+                s = (s + smul(x[o + i], y[o + l])) & M64
+                s = (s + smul(x2[o + i], y2[o + l])) & M64
+        if k < NP:
+            lo0, hi0 = (0, k - 1) if k < H else (k - H + 1, H - 1)
+            for i in range(lo0, hi0 + 1):
+                if i != k - 1:
+                    s = (s + smul(mq[i], nm[k - i])) & M64
+                    macs += 1
+        if mid:
+            lo2, hi2 = rng(j)
+            for i in range(lo2, hi2 + 1):
+                if not (i == j and k < NL) and H + i != k - 1:
+                    s = (s + smul(mq[H + i], nm[H + j - i])) & M64
+                    macs += 1
+        newest = 1 <= k <= NL
+        nn = 1 if k <= H else H + 1
+        if ones == 1 and newest:
+            s = (s + smul(mq[k - 1], nm[nn])) & M64
+            macs += 1
+        e = ss[k - H] if k >= H else 0
+        if mid:
+            lo, hi = rng(j)
+            for i in range(lo, hi + 1):
+                l = j - i
+                e = (e + smul(nx[i], dy[l])) & M64
+                e = (e + smul(nx2[i], dy2[l])) & M64
+            for i in range(lo, hi + 1):
+                if i == j and k < NL:
+                    e = (e + smul(mq[i], ndp[0])) & M64
+                    macs += 1
+                elif H + i != k - 1:
+                    e = (e + smul(dm[i], ndp[j - i])) & M64
+                    macs += 1
+        if k < NL:
+            e = (e + smul(mnin[k], -1)) & M64
+        if H <= k - 1 < NL:
+            e = (e + smul(dm[k - 1 - H], ndp[1])) & M64
+            macs += 1
+        d = (e + s + carry) & M64
+        if ones == 2 and newest:
+            s = (s + smul(mq[k - 1], nm[nn])) & M64
+            d = (d + smul(mq[k - 1], nm[nn])) & M64
+            macs += 2
+        # the schoolbook column without the column's own digit, on plain integers
+        lo, hi = max(0, k - NL + 1), min(k, NL - 1)
+        school = sum(x[i] * y[k - i] + x2[i] * y2[k - i] for i in range(lo, hi + 1)) - (mnin[k] if k < NL else 0) + _s64(carry)
+        school += sum(mq[i] * nm[k - i] for i in (range(k) if k < NL else range(k - NL + 1, NL)))
+        assert _s64(d) == school, ("column", k)
+        if k < NL:
+            mq[k] = sfield(((d & 0xFFFFFFFF) * n0inv) & 0xFFFFFFFF)
+            d = (d + smul(mq[k], nm[0])) & M64
+            school += mq[k] * nm[0]
+            s = (s + smul(mq[k], nm[0 if k < H else H])) & M64
+            macs += 2
+            if k >= H:
+                dm[k - H] = mq[k - H] - mq[k]
+                assert i32(dm[k - H])
+            assert -HB <= mq[k] < HB and school % B == 0
+        else:
+            out[k - NL] = sfield(d)
+        # the finished column, read as a signed 64-bit integer, is the schoolbook column and lies below 2^63
+        assert _s64(d) == school and -(1 << 63) <= school and school + HB < (1 << 63), ("finished column", k)
+        if abs(school) > st.max_d:
+            st.max_d, st.at_d = abs(school), (MUL2, k)
+        if k < H + NP:
+            ss[k] = s
+        else:
+            assert s == 0
+        c = (_s64(d) if k < NL else _s64(d) + HB) >> RB
+        st.max_c = max(st.max_c, abs(c))
+        carries.append(c)
+        carry = c & M64
+    assert i32(_s64(carry))
+    out[NL - 1] = _s64(carry)
+    st.red_macs = macs
+    return out, mq, carries
+
+
+def mul_kara_bal_stage(al, bl, cl, dl, p, st, red=KMRBT_RED):
+    """(a, b) * (c, d) -> (w, v) limb lists as kernel mode PADIC_LDS_KMRBT forms them (mul_kara_lds_bal<PADIC_KMRBT_RED>): the
+    first pass of mul_kara_bal, the second by kara_pass_bal_sum; the relations of mul_kara_bal."""
+    assert red & (1 << MUL2) and red_ones(red)
+    NL = len(al)
+    R = 1 << (RB * NL)
+    nm, n0inv = _bal_ctx(p, NL)
+    assert value(nm) == p
+    w, m = kara_pass_bal(MUL, al, cl, [0] * NL, nm, n0inv, st, kred=True, vf=True, ones=red_ones(red))
+    v, m2, _ = kara_pass_bal_sum(al, dl, bl, cl, m, nm, n0inv, st, ones=red_ones(red))
+    a, b, c, d = value(al), value(bl), value(cl), value(dl)
+    W, M, V, M2 = value(w), value(m), value(v), value(m2)
+    assert W * R == a * c + M * p
+    assert V * R == a * d + b * c - M + M2 * p
+    assert 2 * abs(M) <= R + (R >> 28) and 2 * abs(M2) <= R + (R >> 28)
+    p2 = p * p
+    assert (W + V * p - (a + b * p) * (c + d * p) * pow(R, -1, p2)) % p2 == 0
+    return w, v
+
+
 def in_lazy_range(l, p):
     """The invariant of the balanced engine: |value| < 0.51 p."""
     return 100 * abs(value(l)) < 51 * p
