@@ -28,7 +28,7 @@
  *    output, no word of an input, whatever lies next to them.  Aliasing: an output may be EXACTLY an operand (same address, same
  *    extent) where the call says so.  The calls that state an aliasing rule below (pai_ct_add, pai_ct_mont_mul, pai_ct_add_aligned*,
  *    pai_ct_addn, pai_ct_add_plain, pai_ct_mul*, pai_ct_invert*, pai_ct_scan, pai_ct_pack*, pai_buf_slice, pai_buf_rotate,
- *    pai_modmul) answer any other overlap of the output's byte range with the named operand's byte range with PAI_E_INVALID and
+ *    pai_modmul, pai_partial_decrypt, pai_threshold_combine) answer any other overlap of the output's byte range with the named operand's byte range with PAI_E_INVALID and
  *    launch nothing; in every other call, and for the small operands of these (shifts, entry constants), an output that overlaps
  *    an operand is undefined.  In particular a broadcast row (b_bcast != 0) may be the output only when N == 1: with N > 1 other
  *    waves still load it while output row 0 is stored;
@@ -221,6 +221,46 @@ int pai_recover_r(pai_privkey* sk, const uint32_t* d_ct, size_t N, uint32_t* d_r
  * (the combine steps' sizes). */
 int pai_opening_fold(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* d_m, const uint32_t* d_r, size_t N, const uint32_t* d_e,
                      int e_words, int ebits_max, size_t seg_len, uint32_t* d_lhs, uint32_t* d_rhs, int32_t* d_flag, void* stream);
+
+/* Threshold decryption (extension; no reference counterpart): Damgard-Jurik / Fouque-Poupard-Stern at s = 1
+ * with a trusted dealer.  The dealing is host arithmetic of the Python layer (threshold.py); the library raises ciphertexts to a
+ * shareholder's exponent and combines t partial decryptions with the public key alone.  Honest-but-curious parties only: there are
+ * no verification keys and no proofs.
+ *
+ * A key-share handle owns ONE exponent E (for shareholder i of l: 2 l! s_i, not reduced — the shareholder does not know the
+ * group order), its e_words little-endian words on the device and its sliding-window schedule.  The schedule makes the kernel's control
+ * flow — the run lengths of squarings, the table indices — a function of the share, exactly as the decrypt kernels' schedules are
+ * functions of p - 1 and q - 1: a party that can time or trace the device learns about E what it learns about p and q there.
+ * pai_keyshare_destroy overwrites the exponent and the schedule, on the device and on the host, before freeing them.  The public handle
+ * must outlive every call on the share (not its destruction). */
+typedef struct pai_keyshare pai_keyshare;
+int pai_keyshare_create(const pai_pubkey* pk, const uint32_t* h_e, int e_words, pai_keyshare** out);   /* E > 0, 1 <= e_words <= 1024 */
+void pai_keyshare_destroy(pai_keyshare* share);
+/* d_out[i] = d_ct[i]^E mod n^2, the canonical residue in the wire form; d_ct, d_out: [N][ct_words].  Routes with identical bits:
+ * keys the digit engine serves, from the hand-over edge `PAI_TUNE tpart_min` on (default: where pai_ct_mul reaches its
+ * one-element-per-lane kernel), run k_pow_padic on the share's own schedule (`PAI_TUNE tpart_grid` caps its workgroups: a small batch
+ * then walks the tile loop); every other call — small and mid-size batches, wider keys — takes the routes of pai_ct_mul with E as the
+ * broadcast exponent.  d_out must not overlap d_ct in any way (k_pow_padic reads its input through __restrict__): PAI_E_INVALID, nothing
+ * launched.  Asynchronous on `stream`. */
+int pai_partial_decrypt(pai_keyshare* share, const uint32_t* d_ct, size_t N, uint32_t* d_out, void* stream);
+/* Combines t partial decryptions of the same N ciphertexts:
+ *     d_m[i] = L( prod_j parts_j[i]^(+-mu_j) mod n^2 ) theta mod n,      L(x) = (x - 1) / n,
+ * d_m: [N][n_words].  h_parts: HOST array of t device pointers to [N][ct_words] wire-form rows; h_mu: HOST [t][mu_words] little-endian
+ * magnitudes of the exponents (for a share set S: |2 mu_j|, mu_j = l! prod_(k in S, k != j) k / (k - j)); h_neg: HOST t flags, non-zero =
+ * the exponent is negative; h_theta: HOST [n_words], a residue modulo n ((4 (l!)^2)^-1 mod n).  The members with a negative exponent
+ * form a second product P-, inverted once: x = P+ (P-)^-1.  *d_flag (one device word the caller zeroes): bit 0 — some row's x is not
+ * 1 modulo n: an inconsistent set of partial decryptions (a wrong index, a corrupted row, too few shares); that row of d_m is defined
+ * but meaningless; bit 1 — some row of P- is not a unit modulo n^2 (its row of d_m is then undefined).  d_rowflag: NULL, or int32 [N]
+ * the caller zeroes: 1 on the rows behind bit 0.
+ * PAI_E_INVALID, nothing launched: t outside 1 .. 16, mu_words outside 1 .. 4, a zero coefficient, theta >= n, d_m overlapping a part.
+ * Routes with identical bits: keys the digit engine serves form P+ and P- in one kernel, k_tcomb_padic (the t partials in Montgomery
+ * digit form in a per-lane table, one binary chain per side; `PAI_TUNE tcomb_min`: from this many rows on; default: t >= 3 and pai_partial_decrypt's edge, where it was measured ahead;
+ * `PAI_TUNE tcomb_grid` caps its workgroups); wider keys, and every key under PAI_DISABLE=tcombine, form them by pai_ct_mul per
+ * part and pai_ct_addn per side.  Then pai_ct_invert_flag on P-, pai_ct_add, and k_tfinish (exact division by n, the test, times theta).
+ * Asynchronous on `stream`. */
+int pai_threshold_combine(const pai_pubkey* pk, const uint32_t* const* h_parts, int t, const uint32_t* h_mu, const int32_t* h_neg,
+                          int mu_words, const uint32_t* h_theta, size_t N, uint32_t* d_m, int32_t* d_flag, int32_t* d_rowflag,
+                          void* stream);
 
 /* Owner-side encryption: pai_encrypt / pai_obfuscate by the party that holds p and q — the same bits for the same r.  Served
  * calls (DJN keys whose primes the encryption digit engine accepts, batches from the hand-over edge `PAI_TUNE crtenc_min` on,

@@ -69,6 +69,11 @@ PROTOTYPES = {
     "pai_recover_r": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_opening_fold": (C.c_int, [voidp, voidp, voidp, voidp, C.c_size_t, voidp, C.c_int, C.c_int, C.c_size_t, voidp, voidp, voidp,
                                    voidp]),
+    "pai_keyshare_create": (C.c_int, [voidp, voidp, C.c_int, C.POINTER(voidp)]),
+    "pai_keyshare_destroy": (None, [voidp]),
+    "pai_partial_decrypt": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
+    "pai_threshold_combine": (C.c_int, [voidp, C.POINTER(voidp), C.c_int, voidp, voidp, C.c_int, voidp, C.c_size_t, voidp, voidp, voidp,
+                                        voidp]),
     "pai_encrypt_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_obfuscate_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
     "pai_privkey_crt_table_info": (C.c_int, [voidp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

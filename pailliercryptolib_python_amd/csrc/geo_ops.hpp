@@ -122,6 +122,7 @@ struct FbBases {
 struct PowPadicParams;
 struct CtMulPadicParams;
 struct MexpPadicParams;
+struct TcombPadicParams;
 size_t ctmul_padic_table_words(int nl, int wbits, size_t blocks);
 bool padic_enc_gform_supported();
 // the digit engine's launchers for one limb count (padic_enc_launch.hpp fills one table per translation unit)
@@ -144,6 +145,7 @@ struct PadicEncOps {
     void (*smexp)(hipStream_t, int grid, const MexpPadicParams&, const SmexpArgs&, const uint32_t* e, const uint8_t* sign,
                   uint32_t* out, int nlanes);
     void (*ct_pack)(hipStream_t, int grid, const MexpPadicParams&, int nrows, int slots, int slot_bits, uint32_t* out, int nlanes);
+    void (*tcomb)(hipStream_t, int grid, const TcombPadicParams&, uint32_t* out_pos, uint32_t* out_neg, int n);
 };
 const PadicEncOps* padic_enc_ops(int nl);         // 36 / 72 limbs, nullptr = not served
 const PadicEncOps* padic_enc_ops_36();            // (padic_enc36_kernels.hip)

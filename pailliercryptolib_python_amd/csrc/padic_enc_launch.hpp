@@ -3,6 +3,7 @@
 #pragma once
 #include "geo_ops.hpp"
 #include "kernels_padic_enc.hpp"
+#include "kernels_threshold.hpp"
 #include "launch.hpp"
 
 namespace pai {
@@ -76,6 +77,9 @@ struct EncLaunch {
     static void pow(hipStream_t s, int grid, const PowPadicParams& P, const uint32_t* base, uint32_t* out, int n) {
         launch(k_pow_padic<NL, U>, dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, base, out, n);
     }
+    static void tcomb(hipStream_t s, int grid, const TcombPadicParams& P, uint32_t* out_pos, uint32_t* out_neg, int n) {
+        launch(k_tcomb_padic<NL, U>, dim3(grid), dim3(BLOCK_THREADS), BYTES2, s, P, out_pos, out_neg, n);
+    }
 };
 
 // the table of one limb count: k_encrypt_padic and the g-factoring passes from LE, everything else from L (their row
@@ -94,6 +98,7 @@ PadicEncOps enc_ops() {
     t.mexp = &L::mexp;
     t.smexp = &L::smexp;
     t.ct_pack = &L::ct_pack;
+    t.tcomb = &L::tcomb;
     return t;
 }
 

@@ -24,6 +24,7 @@
 #include "kernels_declat.hpp"
 #include "kernels_crt_lift.hpp"
 #include "kernels_open_fold.hpp"
+#include "kernels_threshold.hpp"
 
 using namespace pai;
 using hbn::Limbs;
@@ -415,7 +416,8 @@ struct ScopedKernelTimer {
 //                                  enc_kara (72-limb DJN encryption on a g-factored table: the row-wise product kernel instead of the
 //                                  Karatsuba-column kernel k_encrypt_padic<72, 12, false, true, true>),
 //                                  pack_padic (pai_ct_pack: the k_segprod levels for every batch),
-//                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key)
+//                                  open_fold (pai_opening_fold: three sparse products modulo n^2 instead of k_open_fold on every key),
+//                                  tcombine (pai_threshold_combine: pai_ct_mul per part and pai_ct_addn per side instead of k_tcomb_padic)
 //   PAI_TUNE="name=value,..."      fb_wbits, fb_digit_wbits, lat_fb_wbits, fb_gform_k, invert_chunk, mexp_wbits, mexp_lanes,
 //                                  mexp_by_rows, lat_rl, lat_mul_rl, lat_enc_tree (largest batch of that small-batch form, 0 = off),
 //                                  segprod_chunk, smexp_chunk, pack_padic_min, scan_chunk (chunk length of pai_ct_scan's levels),
@@ -423,7 +425,10 @@ struct ScopedKernelTimer {
 //                                  rrec_grid (most workgroups per prime of k_rrec_a: a small batch then walks the tile loop),
 //                                  open_chunk (elements per lane of pai_opening_fold; default: smexp_chunk's rule), open_wbits (window of
 //                                  k_open_fold's chain modulo n, 1 .. 4), open_grid (most workgroups of k_open_fold),
-//                                  open_block_rows (most rows of a row block of pai_opening_fold: forces the halving of blocks)
+//                                  open_block_rows (most rows of a row block of pai_opening_fold: forces the halving of blocks),
+//                                  tpart_min (pai_partial_decrypt on k_pow_padic from this many rows on, 0 = every batch), tpart_grid (most
+//                                  workgroups of that kernel), tcomb_min (pai_threshold_combine on k_tcomb_padic from this many rows on),
+//                                  tcomb_grid (most workgroups of k_tcomb_padic)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -567,6 +572,10 @@ struct pai_pubkey {
     // serialises the calls (taken before pk->mu, never under it): the stages of one call run through several locked sections
     mutable DevBuf open_plan, open_table, open_parts, open_rows, open_wide;
     mutable std::mutex open_mu;
+    // pai_threshold_combine (dispatch_threshold.hpp; its calls are serialised by open_mu as well): the partials in digit form per slot of
+    // k_tcomb_padic (sized like ctmul_table at 16 entries), the two sides P+ | P- and the flag word of the inversion, and the
+    // composition route's powers
+    mutable DevBuf tcomb_table, tcomb_sides, tcomb_pow;
     mutable DevBuf seg_partial, seg_plan;      // chunk partials and chunk plans of pai_ct_segment_prod
     mutable DevBuf pack_plan;                  // member list of pai_ct_pack (rows, steps, chain offsets)
     mutable DevBuf quant_acc;                  // limb sums of pai_fp_quantize (four 64-bit words per column / segment)
@@ -1259,6 +1268,9 @@ void pai_pubkey_destroy(pai_pubkey* pk) {
     pk->open_parts.release();
     pk->open_rows.release();
     pk->open_wide.release();
+    pk->tcomb_table.release();
+    pk->tcomb_sides.release();
+    pk->tcomb_pow.release();
     pk->seg_partial.release();
     pk->seg_plan.release();
     pk->pack_plan.release();
@@ -1324,6 +1336,9 @@ int pai_pubkey_trim(pai_pubkey* pk, size_t* freed_bytes) {
         pk->open_parts.release();
         pk->open_rows.release();
         pk->open_wide.release();
+        pk->tcomb_table.release();
+        pk->tcomb_sides.release();
+        pk->tcomb_pow.release();
         pk->seg_partial.release();
         pk->seg_plan.release();
         pk->pack_plan.release();
@@ -1460,6 +1475,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_encrypt_crt.hpp"
 #include "dispatch_recover.hpp"
 #include "dispatch_open_fold.hpp"
+#include "dispatch_threshold.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

@@ -221,6 +221,31 @@ static size_t smexp_chunk(size_t want_lanes, size_t terms) {
 // open_block_rows (test hook): most rows of a row block, which forces the halving that a table too large for the device causes.
 // The API's default segmentation reads path_edges(2) — the first switch point of ct x pt — through pai_path_edges.
 
+// ---- threshold decryption (dispatch_threshold.hpp) ----------------------------------------------------------------------------------
+// pai_partial_decrypt on keys the digit engine serves: k_pow_padic on the share's sliding-window schedule from this many rows on —
+// by default where pai_ct_mul itself reaches its one-element-per-lane kernel (k_ctmul_padic, fixed 5-bit windows: the schedule's
+// 6-bit sliding windows spend fewer products on the same lanes); below, pai_ct_mul's small- and mid-batch routes fill the device
+// with fewer rows.  Measured at 2048-bit keys (profiles/r21/threshold_time.jsonl, ms k_pow_padic / pai_ct_mul's route): 246 / 24.8 at 16 rows, 247 / 72.8 at
+// 4 096, 248 / 79.6 at 16 384, 252 / 282 at 65 536: the hand-over at 49 153 rows (256 CUs) sits between the last two.  PAI_TUNE tpart_min overrides (0 = every batch).
+static size_t tpart_min(size_t ncu, int key_bits, int n_bits) {
+    long long v;
+    if (knob_tune("tpart_min", &v) && v >= 0) return (size_t)v;
+    return std::max(ctmul_mid_max(ncu, n_bits), latency_max_elements(LAT_MUL, key_bits, ncu)) + 1;
+}
+// pai_threshold_combine forms its two sides in k_tcomb_padic from this many rows on.  Measured at 2048-bit keys, 2^16 rows, 16
+// parties (tools/threshold_time.py, profiles/r21/threshold_time.jsonl; ms fused / composition, spreads <= 0.35): t = 2: 14.4 / 14.0,
+// t = 3: 15.3 / 18.5, t = 5: 19.0 / 26.9, t = 16: 35.1 / 79.6 — ahead from three parts on, level at two.  Hence: t >= 3, and the
+// rows from which the composition's pai_ct_mul is itself one element per lane (tpart_min's rule; below, its small- and mid-batch
+// routes fill the device with fewer rows, and nothing was measured there).  PAI_TUNE tcomb_min overrides for every t (0 = every
+// batch); PAI_DISABLE=tcombine leaves the kernel out.
+constexpr size_t TCOMB_NEVER = (size_t)-1;
+static size_t tcomb_min(size_t ncu, int key_bits, int n_bits, int t) {
+    long long v;
+    if (knob_tune("tcomb_min", &v) && v >= 0) return (size_t)v;
+    if (t < 3) return TCOMB_NEVER;
+    return std::max(ctmul_mid_max(ncu, n_bits), latency_max_elements(LAT_MUL, key_bits, ncu)) + 1;
+}
+
 // ---- packed ciphertexts -------------------------------------------------------------------------------------------------------------
 // pai_ct_pack on keys the digit engine serves: from this many OUTPUT rows (chains) on, one chain per lane on digit pairs
 // (k_ct_pack_padic); below, the k_segprod levels, which cut a chain into chunks and so fill the device with few chains.  A lane's

@@ -465,6 +465,33 @@ class PublicKeyHandle:
                                                 _ptr(lhs), _ptr(rhs), _ptr(flag), _stream(self.device)))
         return lhs, rhs, flag
 
+    def threshold_combine(self, parts, coeff, neg, theta: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """pai_threshold_combine: residues [N, n_words] of t partial decryptions (device tensors [N, ct_words]) under the exponents
+        `coeff` (positive ints, |2 mu_j|, at most 128 bits) with the signs `neg`, times theta modulo n.  Returns (m, flag, rowflag):
+        flag one int32 device word (bit 0: some row's product is not 1 modulo n; bit 1: a negative-side product is no unit), rowflag
+        int32 [N] naming the rows of bit 0."""
+        t = len(parts)
+        if not (len(coeff) == t and len(neg) == t):
+            raise ValueError("threshold_combine: one coefficient and one sign per part")
+        for p in parts:
+            self._chk(p, self.ct_words, "part")
+            if p.shape[0] != parts[0].shape[0]:
+                raise ValueError("threshold_combine: parts differ in length")
+        n = parts[0].shape[0] if t else 0
+        mu_words = 4
+        if any(int(c) < 0 or int(c).bit_length() > 32 * mu_words for c in coeff):
+            raise ValueError("threshold_combine: coefficient outside [0, 2^128)")
+        ptrs = (C.c_void_p * max(t, 1))(*[p.data_ptr() for p in parts])
+        mu = ints_to_words([int(c) for c in coeff], mu_words) if t else np.zeros((1, mu_words), dtype=np.uint32)
+        ng = np.asarray([1 if s else 0 for s in neg] or [0], dtype=np.int32)
+        th = int_to_words(int(theta) % self.n, self.n_words)
+        m, flag = self.empty_pt(n), self.new_flag()
+        rowflag = torch.zeros(n, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.pai_threshold_combine(self.h, ptrs, t, mu.ctypes.data_as(C.c_void_p), ng.ctypes.data_as(C.c_void_p),
+                                                     mu_words, th.ctypes.data_as(C.c_void_p), n, _ptr(m), _ptr(flag), _ptr(rowflag),
+                                                     _stream(self.device)))
+        return m, flag, rowflag
+
     def path_edges(self, op: int) -> list:
         """The batch sizes at which the path of `op` may change on this handle's device (pai_path_edges), ascending."""
         buf = (C.c_size_t * 16)()
@@ -752,6 +779,37 @@ class PrivateKeyHandle:
         b, w, j = C.c_size_t(0), C.c_int(0), C.c_int(0)
         _native.check(self.lib.pai_privkey_crt_table_info(self.h, C.byref(b), C.byref(w), C.byref(j)))
         return {"bytes": int(b.value), "window_bits": int(w.value), "windows": int(j.value)}
+
+
+class KeyShareHandle:
+    """Owns a ``pai_keyshare``: the exponent 2 Delta s_i of one shareholder's partial decryptions, bound to a PublicKeyHandle."""
+
+    def __init__(self, pub: PublicKeyHandle, exponent: int):
+        self.lib = pub.lib
+        self.pub = pub
+        if exponent < 0:
+            raise ValueError("KeyShareHandle: negative exponent")
+        ew = max(1, (int(exponent).bit_length() + 31) // 32)
+        e = int_to_words(exponent, ew)
+        h = C.c_void_p()
+        _native.check(self.lib.pai_keyshare_create(pub.h, e.ctypes.data_as(C.c_void_p), ew, C.byref(h)))
+        e[:] = 0
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.pai_keyshare_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def partial_decrypt(self, ct: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pai_partial_decrypt: out[i] = ct[i]^E mod n^2, [N, ct_words] in the wire form; out must not overlap ct."""
+        self.pub._chk(ct, self.pub.ct_words, "ct")
+        out = self.pub.empty_ct(ct.shape[0]) if out is None else out
+        _native.check(self.lib.pai_partial_decrypt(self.h, _ptr(ct), ct.shape[0], _ptr(out), _stream(self.pub.device)))
+        return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -254,6 +254,50 @@ class PaillierPublicKey:
             res[redo] = (again == words[redo]).all(dim=1)
         return ok & res.cpu().numpy()
 
+    # -- threshold decryption (extension, threshold.py): anyone with the public key combines t partial decryptions ----------------
+    def _combine_mantissas(self, parts):
+        from . import threshold as _th
+
+        t = _th.combine_words(self, parts)
+        return _residue_mantissas(self.pubkey.handle, t, self.n.bit_length())
+
+    def combine_raw(self, parts):
+        """What PaillierPrivateKey.raw_decrypt returns for the container the partial decryptions were taken from.  `parts`: at
+        least `threshold` PaillierPartialDecryption of distinct shares (the `threshold` smallest indices are used).  ValueError
+        for an unusable set and for rows that fail the consistency test (a wrong index, a corrupted row, too few shares)."""
+        from . import threshold as _th
+
+        ret = engine.words_to_ints(engine.to_host_words(_th.combine_words(self, parts)))
+        return ret if len(parts[0]) > 1 else ret[0]
+
+    def combine(self, parts):
+        """What PaillierPrivateKey.decrypt returns for that container."""
+        mant, words = self._combine_mantissas(parts)
+        expo = parts[0]._expo
+        if mant is not None:
+            ret = _fp.decode_mantissas(mant, expo)
+        else:
+            ret = _fp.decode_array(words, expo, self.n, self.max_int)
+        return ret if len(parts[0]) > 1 else ret[0]
+
+    def combine_to_numpy(self, parts) -> np.ndarray:
+        """What PaillierPrivateKey.decrypt_to_numpy returns for that container."""
+        mant, words = self._combine_mantissas(parts)
+        expo = parts[0]._expo
+        if mant is not None:
+            return np.ldexp(mant.astype(np.float64), -np.asarray(expo, dtype=np.int64).astype(np.int32))
+        return _fp.decode_float64_array(words, expo, self.n, self.max_int)
+
+    def combine_packed(self, parts) -> np.ndarray:
+        """What PaillierPrivateKey.decrypt_packed returns for the packed container the partial decryptions were taken from."""
+        from . import packed as _packed
+        from . import threshold as _th
+
+        use = _th.select_parts(self, parts, True)
+        view = _PartsAsPacked(use[0])
+        m, wide = _packed._decrypt_fields(lambda _rows: _th.combine_words(self, use, True), self.pubkey.handle, view)
+        return _packed.mantissas_to_float64(m, wide, view.exponent)
+
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
         exponents (pai_fp_encode_at: the plaintext side of ct + plaintext, see encrypt's _align_to), or None when the batch
@@ -367,6 +411,32 @@ class PaillierPublicKey:
         return PaillierEncryptedNumber(self, ipclCipherText(self.pubkey, ct), exponents=expos, length=len(values))
 
 
+def _residue_mantissas(h: engine.PublicKeyHandle, t: torch.Tensor, n_bits: int):
+    """Residues [N, n_words] on the device of `h` -> (int64 mantissas, None) through the device decoder, or (None, residue words
+    on the host) when some element needs the exact big-integer path.  The one decode step behind PaillierPrivateKey.decrypt and
+    PaillierPublicKey.combine."""
+    if n_bits > 66:
+        mant, flag = h.fp_decode_i64(t)
+        if not bool(flag.any()):
+            return mant.cpu().numpy(), None
+    return None, engine.to_host_words(t)
+
+
+class _PartsAsPacked:
+    """The fields packed._decrypt_fields reads of a PaillierPackedNumber, taken from a partial decryption of one."""
+
+    def __init__(self, part):
+        self.slot_bits, self.slots, self.exponent, self.value_bits = part.packing
+        self._length = len(part)
+        self.words = None
+
+    def __len__(self) -> int:
+        return self._length
+
+    def ciphertext(self):
+        return self
+
+
 class PaillierPrivateKey:
     def __init__(self, key: Union[ipclPrivateKey, ipclPublicKey, PaillierPublicKey], p: Optional[int] = None,
                  q: Optional[int] = None):
@@ -417,6 +487,15 @@ class PaillierPrivateKey:
             raise ValueError("PaillierPrivateKey.apply_obfuscator: public key mismatch")
         enc.apply_obfuscator(r=r, _obfuscate=self.prikey.obfuscate_words_)
 
+    def share(self, parties: int, threshold: int, *, seed: Optional[int] = None) -> list:
+        """Extension (threshold.py): deals this key to `parties` shareholders of whom any `threshold` decrypt together
+        (1 <= threshold <= parties <= 16): a list of PaillierKeyShare, index 1 .. parties.  Dealer-based, for honest-but-curious
+        parties: no verification keys, no proofs.  seed: reproducible shares for tests (not secret).  ValueError for a key with
+        gcd(n, lcm(p - 1, q - 1)) != 1."""
+        from . import threshold as _th
+
+        return _th.share_key(self, parties, threshold, seed=seed)
+
     def __getstate__(self):
         return (self.prikey, self.__n, self.__max_int)
 
@@ -463,12 +542,7 @@ class PaillierPrivateKey:
                 return np.concatenate([p[0] for p in parts]), None
             # some element needs the exact host path: the residues of every shard are already there
             return None, np.concatenate([engine.to_host_words(p[2]) for p in parts if p[2] is not None], axis=0)
-        t = self.prikey.decrypt_words(words)
-        if self.__n.bit_length() > 66:
-            mant, flag = pub.handle.fp_decode_i64(t)
-            if not bool(flag.any()):
-                return mant.cpu().numpy(), None
-        return None, engine.to_host_words(t)
+        return _residue_mantissas(pub.handle, self.prikey.decrypt_words(words), self.__n.bit_length())
 
     def raw_decrypt(self, ciphertext: "PaillierEncryptedNumber"):
         """ipcl_python.py:207-217: the raw residues as Python ints (scalar if length 1)."""
