@@ -369,9 +369,11 @@ int pai_ct_multiexp(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
  * prod_j ct_j^(2^(E_s - e_j)) mod n^2 — the exponent-aligned sum of the segment — at one Montgomery product per member plus
  * one per unit of the segment's exponent spread.  d_ct: [N][ct_words] at domain tag `tag` (pai_ct_mont_mul; 0 = wire form,
  * |tag| <= 46); d_rows: uint32 row indices (NULL: member j is row j); d_shift: int32 steps >= 0 (NULL: all 0); d_offsets: int64
- * [S + 1], nondecreasing, d_offsets[S] = the number of members.  A row >= N is skipped and a negative shift counts as 0; either
- * sets bit 2 of the handle's status word (pai_pubkey_status) and never reads outside d_ct.  Long segments are cut into chunks
- * whose partial products are combined by further levels on the handle's scratch (PAI_TUNE segprod_chunk: the chunk length).
+ * [S + 1], nondecreasing, d_offsets[S] = the number of members.  A row >= N is skipped together with its shift and a negative
+ * shift counts as 0, at every chunk length alike; either sets bit 2 of the handle's status word (pai_pubkey_status) and never
+ * reads outside d_ct.  The first member's shift is never applied, but its sign is counted like any other: a negative value there
+ * sets bit 2 as well.  Long segments are cut into chunks whose partial products are combined by further levels on the handle's
+ * scratch (PAI_TUNE segprod_chunk: the chunk length).
  * Reads d_offsets[S] and the longest segment back first (one synchronisation of `stream`); the rest is asynchronous. */
 int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, const uint32_t* d_rows, const int32_t* d_shift,
                         const int64_t* d_offsets, size_t S, uint32_t* d_out, void* stream);
@@ -384,7 +386,7 @@ int pai_ct_segment_prod(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, in
  * of its run's rows up to i.  d_ct: [N][ct_words] at domain tag `tag` (pai_ct_mont_mul; |tag|, |dom_out| <= 46); d_raise, d_step:
  * int32 [N] indexed by row, NULL = all 0; the step of a run's first row is ignored; both may be non-zero on one row.  seg_len must
  * divide N (PAI_E_INVALID otherwise); d_out: [N][ct_words], must not overlap d_ct (PAI_E_INVALID).  A negative raise or step counts as 0 and sets
- * bit 4 of the handle's status word (pai_pubkey_status).  Cost: 1 + [tag != 1] + [dom_out != 1] Montgomery products per row plus
+ * bit 4 of the handle's status word (pai_pubkey_status) — also the step of a run's first row, which is never applied.  Cost: 1 + [tag != 1] + [dom_out != 1] Montgomery products per row plus
  * one per squaring, when there are enough runs to give every lane group of the device one.  Fewer runs are cut into chunks
  * (PAI_TUNE scan_chunk: the chunk length): chunk totals, the scan of the totals (the same call on the handle's scratch, level by
  * level), then the chunks again, seeded with their carries — three launches and about twice the products per level, and no

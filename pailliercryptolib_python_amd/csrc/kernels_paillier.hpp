@@ -1218,7 +1218,7 @@ k_segprod(const MontCtx* __restrict__ ctx, SegArgs A, int w32, const uint32_t* _
                     if (src < 0) {
                         const uint32_t r = A.rows ? A.rows[j] : (uint32_t)j;
                         const int s = A.shift ? A.shift[j] : 0;
-                        ssum += s;
+                        ssum += s > 0 && r < (uint32_t)A.n ? s : 0;   // what a single chain applies: a negative shift is 0, a skipped member brings none
                         bad |= s < 0 || r >= (uint32_t)A.n;
                         sq = has && s > 0 ? s : 0;
                         src = r < (uint32_t)A.n ? (int)r : -1;

@@ -230,6 +230,17 @@ def test_raw_abi_arbitrary_counts_tags_and_guards(monkeypatch):
     with pytest.raises(engine._native.NativeError, match="ct_scan"):
         h.check_status(force=True)
     h.check_status(force=True)                                       # read and cleared: nothing pending any more
+    # the step of a run's first row is never applied; a negative value there is still counted (bit 4), a positive one is not
+    want = want_chain(cts, raise_, step, L, False, nsq)
+    for garbage, flagged in ((-9, True), (1 << 20, False)):
+        first_s = step.copy()
+        first_s[0] = garbage
+        out = h.ct_scan(ct, L, tag=0, dom_out=0, raise_=d_raise, step=torch.from_numpy(first_s).to(h.device))
+        assert engine.words_to_ints(engine.to_host_words(out)) == want, garbage
+        if flagged:
+            with pytest.raises(engine._native.NativeError, match="ct_scan"):
+                h.check_status(force=True)
+        h.check_status(force=True)
 
 
 @pytest.mark.parametrize("L", [256, 65536])

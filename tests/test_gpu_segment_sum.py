@@ -152,6 +152,53 @@ def test_bad_rows_and_negative_shifts_are_guarded():
     h.check_status(force=True)                                       # read and cleared: nothing pending any more
 
 
+@pytest.mark.parametrize("chunk", [None, 2])
+def test_bad_rows_and_negative_shifts_across_levels(monkeypatch, chunk):
+    """The guarded input in a chain that is cut into chunks (found by tests/test_gpu_fuzz_ext.py, segprod round 1): a chunk hands
+    the SUM of its members' shifts to the next level, and that sum must hold what a single chain applies — 0 for a negative shift,
+    nothing for a skipped row.  Members: ct0, ct1 << 1 | (row 9, shift 5: skipped), ct2 with shift -3 | ct1 << 2, ct0 with shift -1."""
+    key, pk, _ = keypair(1024)
+    h = pk.pubkey.handle
+    h.check_status(force=True)
+    _, cts = random_container(pk, key, 3, np.zeros(3, np.int32), 22)
+    ct = engine.to_device_words(engine.ints_to_words(cts, h.ct_words), h.device)
+    rows, shift = [0, 1, 9, 2, 1, 0], [0, 1, 5, -3, 2, -1]
+    nsq, acc = key.nsq, None
+    for r, s in zip(rows, shift):
+        if r < 3:
+            acc = cts[r] if acc is None else pow(acc, 1 << max(s, 0), nsq) * cts[r] % nsq
+    tune(monkeypatch, "segprod_chunk", chunk)
+    out = h.ct_segment_prod(ct, torch.tensor(rows, dtype=torch.int32, device=h.device), torch.tensor(shift, dtype=torch.int32, device=h.device),
+                            torch.tensor([0, 6], dtype=torch.int64, device=h.device))
+    assert engine.words_to_ints(engine.to_host_words(out)) == [acc]
+    with pytest.raises(engine._native.NativeError, match="ct_segment_prod"):
+        h.check_status(force=True)
+    h.check_status(force=True)
+
+
+@pytest.mark.parametrize("chunk", [None, 2])
+def test_first_shift_is_never_applied_and_its_sign_is_counted(monkeypatch, chunk):
+    """The shift of a chain's first member is not applied, whatever it holds; a NEGATIVE value there still sets bit 2 of the status
+    word (include/paillier_hip.h), a positive one does not — in one chain and in a chain cut into chunks."""
+    key, pk, _ = keypair(1024)
+    h = pk.pubkey.handle
+    h.check_status(force=True)
+    _, cts = random_container(pk, key, 5, np.zeros(5, np.int32), 23)
+    ct = engine.to_device_words(engine.ints_to_words(cts, h.ct_words), h.device)
+    nsq = key.nsq
+    want = [pow(pow(pow(cts[0], 2, nsq) * cts[1] % nsq * cts[2] % nsq, 8, nsq) * cts[3] % nsq, 2, nsq) * cts[4] % nsq, cts[2]]
+    tune(monkeypatch, "segprod_chunk", chunk)
+    for garbage, flagged in ((-5, True), (1 << 20, False)):
+        shift = torch.tensor([garbage, 1, 0, 3, 1, garbage], dtype=torch.int32, device=h.device)
+        out = h.ct_segment_prod(ct, torch.tensor([0, 1, 2, 3, 4, 2], dtype=torch.int32, device=h.device), shift,
+                                torch.tensor([0, 5, 6], dtype=torch.int64, device=h.device))
+        assert engine.words_to_ints(engine.to_host_words(out)) == want, garbage
+        if flagged:
+            with pytest.raises(engine._native.NativeError, match="ct_segment_prod"):
+                h.check_status(force=True)
+        h.check_status(force=True)
+
+
 def test_empty_input_and_empty_bins():
     key, pk, _ = keypair(1024)
     x, _ = random_container(pk, key, 0, np.zeros(0, np.int32), 1)
