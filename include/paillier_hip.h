@@ -28,7 +28,7 @@
  *    output, no word of an input, whatever lies next to them.  Aliasing: an output may be EXACTLY an operand (same address, same
  *    extent) where the call says so.  The calls that state an aliasing rule below (pai_ct_add, pai_ct_mont_mul, pai_ct_add_aligned*,
  *    pai_ct_addn, pai_ct_add_plain, pai_ct_mul*, pai_ct_invert*, pai_ct_scan, pai_ct_pack*, pai_buf_slice, pai_buf_rotate,
- *    pai_modmul, pai_partial_decrypt, pai_threshold_combine) answer any other overlap of the output's byte range with the named operand's byte range with PAI_E_INVALID and
+ *    pai_modmul, pai_partial_decrypt, pai_threshold_combine, pai_sha256_rows) answer any other overlap of the output's byte range with the named operand's byte range with PAI_E_INVALID and
  *    launch nothing; in every other call, and for the small operands of these (shifts, entry constants), an output that overlaps
  *    an operand is undefined.  In particular a broadcast row (b_bcast != 0) may be the output only when N == 1: with N > 1 other
  *    waves still load it while output row 0 is stored;
@@ -261,6 +261,27 @@ int pai_partial_decrypt(pai_keyshare* share, const uint32_t* d_ct, size_t N, uin
 int pai_threshold_combine(const pai_pubkey* pk, const uint32_t* const* h_parts, int t, const uint32_t* h_mu, const int32_t* h_neg,
                           int mu_words, const uint32_t* h_theta, size_t N, uint32_t* d_m, int32_t* d_flag, int32_t* d_rowflag,
                           void* stream);
+
+/* The Fiat-Shamir transcript of verifiable threshold decryption (extension; threshold.py holds the byte layout):
+ * SHA-256 (FIPS 180-4) on the device, so that ciphertexts and partial decryptions are hashed where they lie.
+ *
+ * pai_sha256_rows: one digest per row.  h_parts: HOST array of K device pointers, part k [N][h_words[k]] 32-bit words; h_words: HOST K
+ * word counts.  The message of row j is the concatenation over k < K of row j of part k, the words exactly as they lie in memory (for
+ * wire-form residues: their little-endian bytes); d_digest: [N][8] words whose 32 bytes, in memory order, are the standard digest —
+ * hashlib.sha256(message).digest().  1 <= K <= 4, 1 <= h_words[k] <= 4096 (any value, not only multiples of 16), N < 2^31; d_digest
+ * must not overlap a part — anything else is PAI_E_INVALID and launches nothing.  N == 0 is a no-op.  One row per lane, a grid-stride
+ * loop over tiles of 256 rows (`PAI_TUNE sha_grid` caps the workgroups: a small batch then walks the loop).  A 64-byte block that lies
+ * inside one part whose rows keep 16-byte alignment is loaded as four 16-byte vectors, every other block word by word.  Kernel name
+ * k_sha256_rows.  Asynchronous on `stream`.
+ *
+ * pai_sha256_expand: row j of d_e [N][e_words] holds the first 4 e_words bytes of SHA-256(seed || tag || LE64(first_index + j)) as
+ * little-endian words, the top word masked so that the row is below 2^bits.  h_seed32: HOST 32 bytes; h_tag: HOST tag_len bytes,
+ * tag_len <= 15 (the message is one block); 32 <= bits <= 256, e_words = ceil(bits / 32), N < 2^31 — anything else is PAI_E_INVALID and
+ * launches nothing.  first_index + j wraps modulo 2^64.  Kernel name k_sha256_expand.  Asynchronous on `stream`. */
+int pai_sha256_rows(const pai_pubkey* pk, const uint32_t* const* h_parts, const int32_t* h_words, int K, size_t N, uint32_t* d_digest,
+                    void* stream);
+int pai_sha256_expand(const pai_pubkey* pk, const uint8_t* h_seed32, const uint8_t* h_tag, int tag_len, uint64_t first_index, size_t N,
+                      int bits, uint32_t* d_e, int e_words, void* stream);
 
 /* Owner-side encryption: pai_encrypt / pai_obfuscate by the party that holds p and q — the same bits for the same r.  Served
  * calls (DJN keys whose primes the encryption digit engine accepts, batches from the hand-over edge `PAI_TUNE crtenc_min` on,

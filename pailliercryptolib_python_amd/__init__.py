@@ -26,10 +26,10 @@ from .paillier import (  # noqa: F401
     PaillierPublicKey,
 )
 from .packed import PaillierPackedNumber  # noqa: F401
-from .threshold import PaillierKeyShare, PaillierPartialDecryption  # noqa: F401
+from .threshold import PaillierDecryptionProof, PaillierKeyShare, PaillierPartialDecryption, PaillierVerificationKey  # noqa: F401
 
 __all__ = [
-    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "PaillierPackedNumber", "PaillierOpening", "PaillierKeyShare", "PaillierPartialDecryption", "BNUtils",
+    "PaillierKeypair", "PaillierPublicKey", "PaillierPrivateKey", "PaillierEncryptedNumber", "PaillierPackedNumber", "PaillierOpening", "PaillierKeyShare", "PaillierPartialDecryption", "PaillierVerificationKey", "PaillierDecryptionProof", "BNUtils",
     "FixedPointNumber", "context", "hybridControl", "hybridMode",
 ]
 __version__ = "0.1.0"

@@ -74,6 +74,8 @@ PROTOTYPES = {
     "pai_partial_decrypt": (C.c_int, [voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_threshold_combine": (C.c_int, [voidp, C.POINTER(voidp), C.c_int, voidp, voidp, C.c_int, voidp, C.c_size_t, voidp, voidp, voidp,
                                         voidp]),
+    "pai_sha256_rows": (C.c_int, [voidp, C.POINTER(voidp), voidp, C.c_int, C.c_size_t, voidp, voidp]),
+    "pai_sha256_expand": (C.c_int, [voidp, voidp, voidp, C.c_int, C.c_uint64, C.c_size_t, C.c_int, voidp, C.c_int, voidp]),
     "pai_encrypt_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp, voidp]),
     "pai_obfuscate_crt": (C.c_int, [voidp, voidp, voidp, C.c_size_t, voidp]),
     "pai_privkey_crt_table_info": (C.c_int, [voidp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -25,6 +25,7 @@
 #include "kernels_crt_lift.hpp"
 #include "kernels_open_fold.hpp"
 #include "kernels_threshold.hpp"
+#include "kernels_sha256.hpp"
 
 using namespace pai;
 using hbn::Limbs;
@@ -428,7 +429,8 @@ struct ScopedKernelTimer {
 //                                  open_block_rows (most rows of a row block of pai_opening_fold: forces the halving of blocks),
 //                                  tpart_min (pai_partial_decrypt on k_pow_padic from this many rows on, 0 = every batch), tpart_grid (most
 //                                  workgroups of that kernel), tcomb_min (pai_threshold_combine on k_tcomb_padic from this many rows on),
-//                                  tcomb_grid (most workgroups of k_tcomb_padic)
+//                                  tcomb_grid (most workgroups of k_tcomb_padic),
+//                                  sha_grid (most workgroups of k_sha256_rows / k_sha256_expand)
 static const char* list_find(const char* list, const char* name) {       // -> the character behind `name` in the list, or NULL
     if (!list) return nullptr;
     const size_t n = std::strlen(name);
@@ -1476,6 +1478,7 @@ int pai_path_edges(const pai_pubkey* pk, int op, size_t* edges, int cap, int* co
 #include "dispatch_recover.hpp"
 #include "dispatch_open_fold.hpp"
 #include "dispatch_threshold.hpp"
+#include "dispatch_transcript.hpp"
 #include "dispatch_decrypt.hpp"
 
 // ---- multi-GPU helpers (one node) -------------------------------------------------------------------

@@ -492,6 +492,33 @@ class PublicKeyHandle:
                                                      _stream(self.device)))
         return m, flag, rowflag
 
+    def sha256_rows(self, parts, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pai_sha256_rows: int32 [N, 8] whose 32 bytes per row are SHA-256 of the concatenation of row j of every part (1 .. 4
+        contiguous int32 matrices [N, words_k] on this device, 1 <= words_k <= 4096), the words as they lie in memory."""
+        k = len(parts)
+        if not 1 <= k <= 4:
+            raise ValueError("sha256_rows: between 1 and 4 parts")
+        n = parts[0].shape[0]
+        for t in parts:
+            if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != n or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"sha256_rows: expected contiguous int32 [N, words] on {self.device}")
+        out = torch.empty((n, 8), dtype=torch.int32, device=self.device) if out is None else out
+        ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in parts])
+        words = np.asarray([t.shape[1] for t in parts], dtype=np.int32)
+        _native.check(self.lib.pai_sha256_rows(self.h, ptrs, words.ctypes.data_as(C.c_void_p), k, n, _ptr(out), _stream(self.device)))
+        return out
+
+    def sha256_expand(self, seed: bytes, tag: bytes, first_index: int, n: int, bits: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """pai_sha256_expand: int32 [n, ceil(bits / 32)], row j the first bits of SHA-256(seed || tag || LE64(first_index + j)) read
+        little-endian.  seed: 32 bytes; tag: at most 15 bytes; 32 <= bits <= 256."""
+        if len(seed) != 32:
+            raise ValueError("sha256_expand: the seed is 32 bytes")
+        ew = (int(bits) + 31) // 32
+        out = torch.empty((n, ew), dtype=torch.int32, device=self.device) if out is None else out
+        _native.check(self.lib.pai_sha256_expand(self.h, bytes(seed), bytes(tag), len(tag), int(first_index) & (2**64 - 1), n, int(bits),
+                                                 _ptr(out), ew, _stream(self.device)))
+        return out
+
     def path_edges(self, op: int) -> list:
         """The batch sizes at which the path of `op` may change on this handle's device (pai_path_edges), ascending."""
         buf = (C.c_size_t * 16)()

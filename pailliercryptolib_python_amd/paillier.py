@@ -298,6 +298,24 @@ class PaillierPublicKey:
         m, wide = _packed._decrypt_fields(lambda _rows: _th.combine_words(self, use, True), self.pubkey.handle, view)
         return _packed.mantissas_to_float64(m, wide, view.exponent)
 
+    def verify_partial(self, x, part, vk) -> bool:
+        """Checks the proof of a partial decryption `part` of the container `x` (a PaillierEncryptedNumber or PaillierPackedNumber)
+        against the dealing's PaillierVerificationKey: True certifies part_j^2 = x_j^(4 Delta s_i) for every row — the squares are
+        all that combine uses (a row replaced by n^2 - part_j is accepted and combines to the same plaintext) — with error about
+        2^-127 when vk.safe_primes holds and at most 1 / ell for the smallest odd prime ell dividing lcm(p - 1, q - 1) otherwise
+        (threshold.py).  False for a missing proof, a wrong index, key or shape, a row of the part >= n^2, or a failed check;
+        ValueError when a row of x is not below n^2.  Two hashes, two folds and two short exponentiations on the key's home device."""
+        from . import threshold as _th
+
+        return _th.verify_part(self, x, part, vk)
+
+    def verified_parts(self, x, parts, vk):
+        """(good_parts, rejected_indices): the parts whose proofs verify_partial accepts, and the share indices of the others.  Pass
+        good_parts to combine / combine_raw / combine_to_numpy / combine_packed."""
+        from . import threshold as _th
+
+        return _th.verified_parts(self, x, parts, vk)
+
     def _encode_plain_addend(self, values, target: np.ndarray):
         """(device residues [N, n_words], exponents int32[N]) of a float batch or an integer ndarray encoded AT the target
         exponents (pai_fp_encode_at: the plaintext side of ct + plaintext, see encrypt's _align_to), or None when the batch
@@ -487,14 +505,16 @@ class PaillierPrivateKey:
             raise ValueError("PaillierPrivateKey.apply_obfuscator: public key mismatch")
         enc.apply_obfuscator(r=r, _obfuscate=self.prikey.obfuscate_words_)
 
-    def share(self, parties: int, threshold: int, *, seed: Optional[int] = None) -> list:
+    def share(self, parties: int, threshold: int, *, seed: Optional[int] = None, verifiable: bool = False) -> list:
         """Extension (threshold.py): deals this key to `parties` shareholders of whom any `threshold` decrypt together
-        (1 <= threshold <= parties <= 16): a list of PaillierKeyShare, index 1 .. parties.  Dealer-based, for honest-but-curious
-        parties: no verification keys, no proofs.  seed: reproducible shares for tests (not secret).  ValueError for a key with
-        gcd(n, lcm(p - 1, q - 1)) != 1."""
+        (1 <= threshold <= parties <= 16): a list of PaillierKeyShare, index 1 .. parties.  Dealer-based.  verifiable=False: for
+        honest-but-curious parties, no verification keys, no proofs.  verifiable=True: every share carries the dealing's
+        PaillierVerificationKey (share.verification_key: v = u^2, v_i = v^(Delta s_i), safe_primes, small_order_factor), so that
+        partial_decrypt(x, prove=True) can prove and PaillierPublicKey.verify_partial can check; the shares are the same bits.
+        seed: reproducible shares for tests (not secret).  ValueError for a key with gcd(n, lcm(p - 1, q - 1)) != 1."""
         from . import threshold as _th
 
-        return _th.share_key(self, parties, threshold, seed=seed)
+        return _th.share_key(self, parties, threshold, seed=seed, verifiable=verifiable)
 
     def __getstate__(self):
         return (self.prikey, self.__n, self.__max_int)
