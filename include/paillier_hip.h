@@ -19,7 +19,13 @@
  *    of the same key material on different devices are independent.  Only pai_ct_invert (it reports
  *    non-invertible inputs; pai_ct_invert_async + pai_pubkey_status is the asynchronous form), pai_pubkey_status,
  *    pai_pubkey_trim and pai_ct_pow2 without a hint return after their stream work has completed; everything else,
- *    pai_decrypt and pai_modexp_fixed (its host exponent is copied to pinned staging) included, is asynchronous;
+ *    pai_decrypt and pai_modexp_fixed (its host exponent is copied to pinned staging) included, is asynchronous.  The library keeps HIP
+ *    events beyond a call — one per handle that orders its scratch, one per slot of the calling thread's host staging ring — and waits
+ *    for them in later calls, possibly after the caller has destroyed the stream they were last recorded on.  What is established about
+ *    that: with the staging ring's events last recorded on destroyed streams, hipEventSynchronize has failed in the ring with
+ *    hipErrorCapturedEvent although nothing captures.  Until that is settled, keep a stream alive while handles (and, for host staging,
+ *    the thread) that were used with it live on; tests/test_gpu_stream_contract.py, which holds this contract on non-blocking streams,
+ *    keeps its streams for the life of the process for that reason;
  *  - memory contract (held by tests/test_gpu_memory_contract.py).  Alignment: a device pointer needs the alignment of its C
  *    type and no more — 4 bytes for uint32_t / int32_t rows, 8 for double / int64_t / uint64_t, 1 for uint8_t; row r of a batch
  *    is a valid operand whatever the row length (rows of 34 or 102 words are not 16-byte multiples).  Kernels that move rows as
@@ -92,7 +98,10 @@ int pai_stream_sync(int device, void* stream);
  * PAI_HOST_STAGE_MAX bytes, each part 16-byte aligned) into one slot of a pinned, device-mapped ring of the calling thread
  * and returns, per part, a pointer a kernel may READ through directly.  Contract: the pointers may be passed as read-only
  * device operands (exponents, shifts, codec inputs) of calls enqueued on `stream` BEFORE the calling thread's next
- * pai_host_stage for that device; the library keeps the slot intact until those calls have executed. */
+ * pai_host_stage for that device; the library keeps the slot intact until those calls have executed.  It marks the point behind
+ * them on `stream` at the calling thread's NEXT pai_host_stage for that device: `stream` must still exist then (a caller that destroys
+ * it first stages once more on a stream that lives on, NULL for instance).  The calls that stage and launch in one (the two _host calls
+ * below, pai_threshold_combine) mark that point themselves before they return and never touch their stream again. */
 #define PAI_HOST_STAGE_MAX 4096
 int pai_host_stage(int device, int parts, const void* const* h_src, const size_t* bytes, void* stream, void** d_ptrs);
 /* pai_ct_add_aligned / pai_ct_mul (below) with their small operand — the shifts, the exponents — still on the HOST (at most
@@ -502,7 +511,8 @@ int pai_ct_pack(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, i
  * packed rows of k slots of b bits: `count` consecutive rows become one row of count k slots (element i stays element i, in row
  * i / (count k), slot i % (count k)); pai_ct_pack(b, k) is the case step_bits = b, count = k, with identical bits.  Constraints:
  * step_bits >= 8, count >= 1 and count step_bits <= bits(n) - 2; anything else is PAI_E_INVALID and launches nothing.  Arguments,
- * routes and knobs otherwise as pai_ct_pack (the hand-over counts output rows; PAI_DISABLE=pack_padic, PAI_TUNE pack_padic_min). */
+ * routes and knobs otherwise as pai_ct_pack (the hand-over counts output rows; PAI_DISABLE=pack_padic, PAI_TUNE pack_padic_min): the
+ * level driver synchronises `stream` once, one chain per lane is asynchronous. */
 int pai_ct_pack_step(const pai_pubkey* pk, const uint32_t* d_ct, size_t N, int tag, int step_bits, int count, uint32_t* d_out,
                      void* stream);
 
@@ -540,7 +550,10 @@ int pai_shard_plan(size_t N, int nshards, int shard, size_t* begin, size_t* coun
 /* Single-process fan-out over the visible devices (one key handle per device): gathers row shards living on
  * devices[i] (rows[i] rows of row_words words each, back to back in shard order) into d_out on dst_device, or
  * scatters d_in on src_device into the shards — peer copies over xGMI, all shards in flight at once; returns when
- * the copies have completed.  (One-process-per-GPU jobs gather with RCCL instead: sharding.py.) */
+ * the copies have completed.  (One-process-per-GPU jobs gather with RCCL instead: sharding.py.)
+ * The two calls take no stream: they copy on the NULL streams of the devices involved and wait for those.  Shards (or d_in) that
+ * were produced on a non-blocking stream are not ordered before the copies by anything the library does: the caller synchronises
+ * that stream first, as engine._peer_copy does (torch.cuda.synchronize on every device involved). */
 int pai_gather(int nshards, const int* devices, const void* const* d_shards, const size_t* rows, int row_words,
                int dst_device, void* d_out);
 int pai_scatter(int nshards, const int* devices, void* const* d_shards, const size_t* rows, int row_words,

@@ -73,6 +73,7 @@ int pai_ct_add_aligned_host(const pai_pubkey* pk, const uint32_t* d_a, const uin
         const size_t len[1] = {N * sizeof(int32_t)};
         void* dp[1] = {nullptr};
         host_stage_parts(pk->device, 1, src, len, stream, dp);
+        StageSeal seal_(pk->device);                                           // the slot's only reader is queued when this scope ends
         add_aligned_common(pk, d_a, d_b, b_bcast, static_cast<const int32_t*>(dp[0]), N, d_out, nullptr, stream);
     });
 }

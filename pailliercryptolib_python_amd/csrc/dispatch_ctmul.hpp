@@ -227,6 +227,7 @@ int pai_ct_mul_host(const pai_pubkey* pk, const uint32_t* d_ct, const uint32_t* 
         dp0 = dp[0];
     });
     if (rc != PAI_OK) return rc;
+    StageSeal seal_(pk->device);                                                // the slot's only reader is queued when this scope ends
     return pai_ct_mul(pk, d_ct, static_cast<const uint32_t*>(dp0), e_words, ebits_max, e_bcast, N, d_out, stream);
 }
 

@@ -224,15 +224,19 @@ bool encrypt_crt(pai_privkey* sk, const uint32_t* d_m, const uint32_t* d_r, uint
     std::lock_guard<std::mutex> lkp(pk->mu);
     g_last_times.clear();
     build_crt_tables(sk);
-    if (C.zeros_rows < N) {
-        C.zeros.ensure(N * 4);
-        HIP_CHECK(hipMemset(C.zeros.p, 0, N * 4));          // (synchronous: ordered before the kernels of any stream)
-        C.zeros_rows = N;
-    }
+    const bool grow_zeros = C.zeros_rows < N;
+    if (grow_zeros) C.zeros.ensure(N * 4);                  // (a grown buffer is a fresh one: DevBuf::ensure frees the old one, which waits for the device)
     C.cs.ensure(2 * N * (size_t)C.sw * 4);
     C.lifted.ensure(N * (size_t)pk->ct_words * 4);
     OrderScope order_sk(sk->order, s);
     OrderScope order_pk(pk->order, s);
+    if (grow_zeros) {
+        // filled on the call's own stream, inside the scratch order: this call's kernels follow it on `s`, and a later call on
+        // another stream waits for the event this scope records.  (A memset on the null stream is ordered before nothing that
+        // runs on a non-blocking stream, and hipMemset does not promise to have completed when it returns.)
+        HIP_CHECK(hipMemsetAsync(C.zeros.p, 0, N * 4, s));
+        C.zeros_rows = N;
+    }
     const size_t tiles = (N + BLOCK_THREADS - 1) / BLOCK_THREADS;
     const int pgrid = (int)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)pk->dev.ncu));
     const auto enc = launcher(padic_enc_ops(C.nl), &PadicEncOps::encrypt, "no digit-engine encrypt kernel for this limb count");

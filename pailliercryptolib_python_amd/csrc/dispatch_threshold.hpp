@@ -160,6 +160,7 @@ int pai_threshold_combine(const pai_pubkey* pk, const uint32_t* const* h_parts, 
             d_thR = static_cast<const uint32_t*>(dp[0]);
             d_mu = static_cast<const uint32_t*>(dp[1]);
         }
+        StageSeal seal_(pk->device);                              // theta and the coefficients: their last reader (k_tfinish) is queued when this scope ends
         const bool has_neg = neg_mask != 0, has_pos = (~neg_mask & ((1u << t) - 1u)) != 0;
         const bool fused = pk->penc_nl != 0 && !knob_disabled("tcombine") && N >= tcomb_min((size_t)pk->dev.ncu, pk->key_bits, hbn::bitlen(pk->n), t);
         uint32_t *Pp = nullptr, *Pn = nullptr;

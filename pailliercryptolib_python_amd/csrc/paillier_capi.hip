@@ -971,6 +971,36 @@ void host_stage_parts(int device, int parts, const void* const* h_src, const siz
     R.pending = k;
     R.pending_stream = (hipStream_t)stream;
 }
+// The calls that stage and launch in one (pai_ct_mul_host, pai_ct_add_aligned_host, pai_threshold_combine) mark the point behind the
+// slot's readers on their own stream before they return, on the failing paths too (StageSeal), instead of leaving it to the
+// thread's next staging: the caller may have destroyed the stream by then.  Never throws: where the event cannot be recorded,
+// everything enqueued has to finish, as in host_stage_parts.
+void host_stage_seal(int device) noexcept {
+    if (device < 0 || (int)tl_stage.per_device.size() <= device || !tl_stage.per_device[device]) return;
+    HostStageRing& R = *tl_stage.per_device[device];
+    if (R.pending < 0) return;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(device);
+    const int k = R.pending;
+    R.pending = -1;
+    if ((R.ev[k] || hipEventCreateWithFlags(&R.ev[k], hipEventDisableTiming) == hipSuccess) &&
+        hipEventRecord(R.ev[k], R.pending_stream) == hipSuccess) {
+        R.recorded[k] = true;
+    } else {
+        (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+        R.recorded[k] = false;
+    }
+    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+}
+struct StageSeal {
+    int device;
+    explicit StageSeal(int d) : device(d) {}
+    ~StageSeal() { host_stage_seal(device); }
+    StageSeal(const StageSeal&) = delete;
+    StageSeal& operator=(const StageSeal&) = delete;
+};
 }  // namespace
 extern "C" {
 

@@ -20,6 +20,7 @@ import numpy as np
 from oracle import paillier_oracle as orc
 from pailliercryptolib_python_amd import _native
 from tests import _fuzz_ext as fz
+from tests import _streams
 from tests._util import DevArray, host_ptr, ints_to_limbs, limbs_to_ints
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -91,8 +92,8 @@ def has(names, kernel):
 
 
 class Checker:
-    def __init__(self, case, seed, cov):
-        self.c, self.seed, self.cov, self.checks = case, seed, cov, 0
+    def __init__(self, case, seed, cov, profiled=True):
+        self.c, self.seed, self.cov, self.checks, self.profiled = case, seed, cov, 0, profiled
 
     def ran(self, lib, label=""):
         names = ran(lib)
@@ -108,6 +109,8 @@ class Checker:
                 raise AssertionError(fz.reproducer(self.c, self.seed, run, what, i, g, w))
 
     def that(self, ok, run, what, got=None, want=None):
+        if what.startswith("kernels") and not self.profiled:
+            return                                   # the kernel timers synchronise: a delayed stream runs without the profile
         self.checks += 1
         if not ok:
             raise AssertionError(fz.reproducer(self.c, self.seed, run, what, "-", got, want))
@@ -118,151 +121,179 @@ def tagged(h, vals, tag):
     return [v * f % h.key.nsq for v in vals]
 
 
-def dev(nk, vals, words=None):
-    return DevArray(ints_to_limbs(vals, words or nk.cw))
+def placement(stream):
+    """`stream` of a runner: None — resident operands, the null stream; or a tests/_streams.Late — value operands arrive behind its
+    blocker, the calls go to its stream"""
+    return _streams.Resident() if stream is None else stream
 
 
-def opt(arr):
-    return None if arr is None else DevArray(arr)
+def dev(nk, vals, words=None, st=None):
+    """a value operand: rows of residues or exponents"""
+    return (st or _streams.Resident()).value(ints_to_limbs(vals, words or nk.cw))
+
+
+def opt(arr, st=None):
+    """an operand the kernels index with (rows, offsets, shifts, steps, signs): resident on every placement"""
+    return None if arr is None else (st or _streams.Resident()).resident(arr)
 
 
 def ptr(d):
     return None if d is None else d.ptr
 
 
-def status(nk, clear=1):
+def status(nk, clear=1, stream=None):
     st = C.c_int(-1)
-    _native.check(nk.lib.pai_pubkey_status(nk.pk, C.byref(st), clear, None))
+    _native.check(nk.lib.pai_pubkey_status(nk.pk, C.byref(st), clear, stream))
     return st.value
 
 
 # ---- the families ------------------------------------------------------------------------------------------------------------------
-def run_segprod(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
-    dct = dev(nk, tagged(h, c["cts"], c["tag"]))
-    drows, dshift, doff = opt(c["rows"]), opt(c["shift"]), DevArray(c["offsets"])
-    out = DevArray(shape=(c["S"], nk.cw))
+def run_segprod(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
+    dct = dev(nk, tagged(h, c["cts"], c["tag"]), st=st)
+    drows, dshift, doff = opt(c["rows"], st), opt(c["shift"], st), st.resident(c["offsets"])
+    out = st.out((c["S"], nk.cw))
     for run in c["runs"]:
         with with_knobs(run):
-            _native.check(lib.pai_ct_segment_prod(nk.pk, dct.ptr, c["N"], c["tag"], ptr(drows), ptr(dshift), doff.ptr, c["S"], out.ptr, None))
+            st.issue()
+            _native.check(lib.pai_ct_segment_prod(nk.pk, dct.ptr, c["N"], c["tag"], ptr(drows), ptr(dshift), doff.ptr, c["S"], out.ptr, st.stream))
+            st.issued(syncs=True)
             names = ck.ran(lib)
-            ck.rows(run, "pai_ct_segment_prod", limbs_to_ints(out.get()), c["want"])
+            ck.rows(run, "pai_ct_segment_prod", limbs_to_ints(st.read(out)), c["want"])
             ck.that(set(names) == {"k_segprod:"}, run, "kernels", names)
             if len(names) >= 2:
                 ck.cov.add("k_segprod:levels>=2")
-            st = status(nk)
-            ck.that(st == c["status_bit"], run, "status word", st, c["status_bit"])
+            sw = status(nk, stream=st.stream)
+            ck.that(sw == c["status_bit"], run, "status word", sw, c["status_bit"])
 
 
-def run_scan(h, c, ck, with_knobs):
-    nk, lib, M = h.nk, h.nk.lib, h.key.nsq
-    dct = dev(nk, tagged(h, c["cts"], c["tag"]))
-    draise, dstep = opt(c["raise"]), opt(c["step"])
-    out = DevArray(shape=(c["N"], nk.cw))
+def run_scan(h, c, ck, with_knobs, stream=None):
+    nk, lib, M, st = h.nk, h.nk.lib, h.key.nsq, placement(stream)
+    dct = dev(nk, tagged(h, c["cts"], c["tag"]), st=st)
+    draise, dstep = opt(c["raise"], st), opt(c["step"], st)
+    out = st.out((c["N"], nk.cw))
     want = tagged(h, c["want"], c["dom_out"])
     for run in c["runs"]:
         with with_knobs(run):
+            st.issue()
             _native.check(lib.pai_ct_scan(nk.pk, dct.ptr, c["N"], c["tag"], c["dom_out"], c["seg_len"], c["reverse"], ptr(draise), ptr(dstep),
-                                          out.ptr, None))
+                                          out.ptr, st.stream))
+            st.issued()
             names = ck.ran(lib)
-            ck.rows(run, "pai_ct_scan", limbs_to_ints(out.get()), want)
+            ck.rows(run, "pai_ct_scan", limbs_to_ints(st.read(out)), want)
             ck.that(set(names) == {"k_segscan:"}, run, "kernels", names)
             if len(names) >= 2:
                 ck.cov.add("k_segscan:carry")
-            st = status(nk)
-            ck.that(st == c["status_bit"], run, "status word", st, c["status_bit"])
+            sw = status(nk, stream=st.stream)
+            ck.that(sw == c["status_bit"], run, "status word", sw, c["status_bit"])
 
 
-def run_smexp(h, c, ck, with_knobs):
+def run_smexp(h, c, ck, with_knobs, stream=None):
+    st = placement(stream)
     handles = [("", h.nk)]
     if c["second_handle_padic_off"]:
         handles.append(("[PAI_DISABLE=padic handle]", h.padic_off(with_knobs)))
     for label, nk in handles:
         lib = nk.lib
-        dbase, dinv = dev(nk, c["base"]), (dev(nk, c["inv"]) if c["inv"] is not None else None)
-        didx, de = DevArray(c["bidx"]), dev(nk, c["e"], c["e_words"])
-        dsign, doff = opt(c["sign"]), DevArray(c["offsets"])
-        out = DevArray(shape=(c["S"], nk.cw))
+        dbase, dinv = dev(nk, c["base"], st=st), (dev(nk, c["inv"], st=st) if c["inv"] is not None else None)
+        didx, de = st.resident(c["bidx"]), dev(nk, c["e"], c["e_words"], st=st)
+        dsign, doff = opt(c["sign"], st), st.resident(c["offsets"])
+        out = st.out((c["S"], nk.cw))
         digit = fz.digit_served(h.key.n.bit_length()) and not label
         for run in c["runs"]:
             with with_knobs(run):
+                st.issue()
                 _native.check(lib.pai_ct_sparse_multiexp(nk.pk, dbase.ptr, ptr(dinv), c["N"], didx.ptr, de.ptr, c["e_words"], c["ebits"], ptr(dsign),
-                                                         c["T"], doff.ptr, c["S"], out.ptr, None))
+                                                         c["T"], doff.ptr, c["S"], out.ptr, st.stream))
+                st.issued(syncs=True)
                 names = ck.ran(lib, "[digit pairs]" if digit else "[lane groups]")          # inferred from the handle (module docstring)
-                ck.rows(run, "pai_ct_sparse_multiexp" + label, limbs_to_ints(out.get()), c["want"])
+                ck.rows(run, "pai_ct_sparse_multiexp" + label, limbs_to_ints(st.read(out)), c["want"])
                 ck.that(has(names, "k_smexp"), run, "kernels" + label, names)
-                st = status(nk)
-                ck.that(st == c["status_bit"], run, "status word" + label, st, c["status_bit"])
+                sw = status(nk, stream=st.stream)
+                ck.that(sw == c["status_bit"], run, "status word" + label, sw, c["status_bit"])
 
 
-def run_pack(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
+def run_pack(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
     N, b, k, N2, step, count = c["N"], c["slot_bits"], c["slots"], c["N_step"], c["step_bits"], c["count"]
-    dct = dev(nk, tagged(h, c["cts"], c["tag"]))
-    out = DevArray(shape=(len(c["want"]), nk.cw))
-    out2 = DevArray(shape=(len(c["want_step"]), nk.cw))
+    dct = dev(nk, tagged(h, c["cts"], c["tag"]), st=st)
+    out = st.out((len(c["want"]), nk.cw))
+    out2 = st.out((len(c["want_step"]), nk.cw))
     digit = fz.digit_served(h.key.n.bit_length()) and c["tag"] == 0
     for run in c["runs"]:
         with with_knobs(run):
             fused = digit and not run["disable"]
             for what, call, o, want in (
-                    (f"pai_ct_pack({b}, {k})", lambda: lib.pai_ct_pack(nk.pk, dct.ptr, N, c["tag"], b, k, out.ptr, None), out, c["want"]),
-                    (f"pai_ct_pack_step({b}, {k})", lambda: lib.pai_ct_pack_step(nk.pk, dct.ptr, N, c["tag"], b, k, out.ptr, None), out, c["want"]),
-                    (f"pai_ct_pack_step({step}, {count})", lambda: lib.pai_ct_pack_step(nk.pk, dct.ptr, N2, c["tag"], step, count, out2.ptr, None),
+                    (f"pai_ct_pack({b}, {k})", lambda: lib.pai_ct_pack(nk.pk, dct.ptr, N, c["tag"], b, k, out.ptr, st.stream), out, c["want"]),
+                    (f"pai_ct_pack_step({b}, {k})", lambda: lib.pai_ct_pack_step(nk.pk, dct.ptr, N, c["tag"], b, k, out.ptr, st.stream), out, c["want"]),
+                    (f"pai_ct_pack_step({step}, {count})", lambda: lib.pai_ct_pack_step(nk.pk, dct.ptr, N2, c["tag"], step, count, out2.ptr, st.stream),
                      out2, c["want_step"])):
+                st.issue()
                 _native.check(call())
+                st.issued(syncs=not fused)                 # the level driver reads its sizes back; one chain per lane is asynchronous
                 names = ck.ran(lib)
-                ck.rows(run, what, limbs_to_ints(o.get()), want)
+                ck.rows(run, what, limbs_to_ints(st.read(o)), want)
                 ck.that(has(names, "k_ct_pack_padic") == fused and (fused or set(names) == {"k_segprod:"}), run, "kernels of " + what, names)
 
 
-def run_open(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
+def run_open(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
     N = c["N"]
-    dct, outr = dev(nk, c["cts"]), DevArray(shape=(N, nk.nw))
-    _native.check(lib.pai_recover_r(nk.sk, dct.ptr, N, outr.ptr, None))
+    dct, outr = dev(nk, c["cts"], st=st), st.out((N, nk.nw))
+    st.issue()
+    _native.check(lib.pai_recover_r(nk.sk, dct.ptr, N, outr.ptr, st.stream))
+    st.issued()
     names = ck.ran(lib)
-    ck.rows("-", "pai_recover_r", limbs_to_ints(outr.get()), c["want_r"])
+    ck.rows("-", "pai_recover_r", limbs_to_ints(st.read(outr)), c["want_r"])
     ck.that(has(names, "k_rrec_a") and has(names, "k_rrec_b"), "-", "kernels of pai_recover_r", names)
     S = len(c["want_lhs"])
-    fct, fm, fr, fe = dev(nk, c["fold_ct"]), dev(nk, c["fold_m"], nk.nw), dev(nk, c["fold_r"], nk.nw), dev(nk, c["e"], c["e_words"])
+    fct, fm, fr = dev(nk, c["fold_ct"], st=st), dev(nk, c["fold_m"], nk.nw, st=st), dev(nk, c["fold_r"], nk.nw, st=st)
+    fe = dev(nk, c["e"], c["e_words"], st=st)
+    lhs, rhs = st.out((S, nk.cw)), st.out((S, nk.cw))
     for run in c["runs"]:
         with with_knobs(run):
-            lhs, rhs, flag = DevArray(shape=(S, nk.cw)), DevArray(shape=(S, nk.cw)), DevArray(np.zeros(1, dtype=np.int32))
+            flag = st.resident(np.zeros(1, dtype=np.int32))
+            st.issue()
             _native.check(lib.pai_opening_fold(nk.pk, fct.ptr, fm.ptr, fr.ptr, N, fe.ptr, c["e_words"], c["ebits"], c["seg_len"], lhs.ptr, rhs.ptr,
-                                               flag.ptr, None))
+                                               flag.ptr, st.stream))
+            st.issued(syncs=True)
             names = ck.ran(lib)
-            ck.rows(run, "pai_opening_fold lhs", limbs_to_ints(lhs.get()), c["want_lhs"])
-            ck.rows(run, "pai_opening_fold rhs", limbs_to_ints(rhs.get()), c["want_rhs"])
-            got = int(flag.get()[0])
+            ck.rows(run, "pai_opening_fold lhs", limbs_to_ints(st.read(lhs)), c["want_lhs"])
+            ck.rows(run, "pai_opening_fold rhs", limbs_to_ints(st.read(rhs)), c["want_rhs"])
+            got = int(st.read(flag)[0])
             ck.that(got & 1 == c["want_flag"], run, "pai_opening_fold flag", got, c["want_flag"])
             fused = fz.digit_served(h.key.n.bit_length()) and not run["disable"]
             ck.that(has(names, "k_open_fold") == fused, run, "kernels of pai_opening_fold", names)
 
 
-def run_crtenc(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
+def run_crtenc(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
     N = c["N"]
-    dm, dr = dev(nk, c["m"], nk.nw), dev(nk, c["r"], nk.rw)
+    dm, dr = dev(nk, c["m"], nk.nw, st=st), dev(nk, c["r"], nk.rw, st=st)
+    out = st.out((N, nk.cw))
     for run in c["runs"]:                                  # the served route first: a handle's first call decides its CRT constants
         with with_knobs(run):
-            out = DevArray(shape=(N, nk.cw))
-            _native.check(lib.pai_encrypt_crt(nk.sk, dm.ptr, dr.ptr, N, out.ptr, None))
+            st.issue()
+            _native.check(lib.pai_encrypt_crt(nk.sk, dm.ptr, dr.ptr, N, out.ptr, st.stream))
+            st.issued()
             names = ck.ran(lib)
-            ck.rows(run, "pai_encrypt_crt", limbs_to_ints(out.get()), c["want_enc"])
+            ck.rows(run, "pai_encrypt_crt", limbs_to_ints(st.read(out)), c["want_enc"])
             lift = c["served"] and not run["disable"]
             ck.that(has(names, "k_crt_lift") == lift and (lift or has(names, "k_encrypt")), run, "kernels of pai_encrypt_crt", names)
-            ct = dev(nk, c["cts"])
-            _native.check(lib.pai_obfuscate_crt(nk.sk, ct.ptr, dr.ptr, N, None))
+            ct = dev(nk, c["cts"], st=st)
+            st.issue()
+            _native.check(lib.pai_obfuscate_crt(nk.sk, ct.ptr, dr.ptr, N, st.stream))
+            st.issued()
             names = ck.ran(lib)
-            ck.rows(run, "pai_obfuscate_crt", limbs_to_ints(ct.get()), c["want_obf"])
+            ck.rows(run, "pai_obfuscate_crt", limbs_to_ints(st.read(ct)), c["want_obf"])
             ck.that(has(names, "k_crt_lift") == lift and (lift or has(names, "k_encrypt")), run, "kernels of pai_obfuscate_crt", names)
 
 
-def run_tpart(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
+def run_tpart(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
     N = c["N"]
-    dct = dev(nk, c["cts"])
+    dct = dev(nk, c["cts"], st=st)
+    out = st.out((N, nk.cw))
     for run in c["runs"]:
         with with_knobs(run):
             for E, want in zip(c["E"], c["want"]):
@@ -270,10 +301,11 @@ def run_tpart(h, c, ck, with_knobs):
                 sh = C.c_void_p()
                 _native.check(lib.pai_keyshare_create(nk.pk, host_ptr(ints_to_limbs([E], ew)), ew, C.byref(sh)))
                 try:
-                    out = DevArray(shape=(N, nk.cw))
-                    _native.check(lib.pai_partial_decrypt(sh, dct.ptr, N, out.ptr, None))
+                    st.issue()
+                    _native.check(lib.pai_partial_decrypt(sh, dct.ptr, N, out.ptr, st.stream))
+                    st.issued()
                     names = ck.ran(lib)
-                    got = limbs_to_ints(out.get())
+                    got = limbs_to_ints(st.read(out))
                 finally:
                     lib.pai_keyshare_destroy(sh)
                 what = f"pai_partial_decrypt E of {E.bit_length()} bits, {bin(E).count('1')} set"
@@ -283,40 +315,46 @@ def run_tpart(h, c, ck, with_knobs):
                     ck.that(has(names, "k_ctmul"), run, "kernels of " + what, names)
 
 
-def run_tcomb(h, c, ck, with_knobs):
-    nk, lib = h.nk, h.nk.lib
+def run_tcomb(h, c, ck, with_knobs, stream=None):
+    nk, lib, st = h.nk, h.nk.lib, placement(stream)
     N, t = c["N"], c["t"]
     mu = ints_to_limbs(c["mu"], c["mu_words"])
     neg = np.asarray(c["neg"], dtype=np.int32)
     theta = ints_to_limbs([c["theta"]], nk.nw)
     digit = fz.digit_served(h.key.n.bit_length())
+    m = st.out((N, nk.nw))
 
     def combine(parts):
         ptrs = (C.c_void_p * t)(*[p.ptr.value for p in parts])
-        m, flag, rowflag = DevArray(shape=(N, nk.nw)), DevArray(np.zeros(1, dtype=np.int32)), DevArray(np.zeros(N, dtype=np.int32))
+        flag, rowflag = st.resident(np.zeros(1, dtype=np.int32)), st.resident(np.zeros(N, dtype=np.int32))
+        st.issue()
         _native.check(lib.pai_threshold_combine(nk.pk, ptrs, t, host_ptr(mu), host_ptr(neg), c["mu_words"], host_ptr(theta), N, m.ptr, flag.ptr,
-                                                rowflag.ptr, None))
-        _native.check(lib.pai_stream_sync(0, None))
-        return limbs_to_ints(m.get()), int(flag.get()[0]), rowflag.get().tolist()
+                                                rowflag.ptr, st.stream))
+        st.issued()
+        _native.check(lib.pai_stream_sync(0, st.stream))
+        return limbs_to_ints(st.read(m)), int(st.read(flag)[0]), st.read(rowflag).tolist()
 
-    parts = [dev(nk, p) for p in c["parts"]]
+    parts = [dev(nk, p, st=st) for p in c["parts"]]
+    poisoned = None
+    if c["poison"] is not None:
+        j, i, v = c["poison"]
+        bad = list(c["parts"][j])
+        bad[i] = v
+        poisoned = parts[:j] + [dev(nk, bad, st=st)] + parts[j + 1:]
     seen = []
     for run in c["runs"]:
         with with_knobs(run):
-            got, flag, rowflag = combine(parts)
+            got, fl, rf = combine(parts)
             names = ck.ran(lib)
-            ck.rows(run, "pai_threshold_combine d_rowflag", rowflag, c["want_rowflag"])
-            ck.that(flag == int(any(c["want_rowflag"])), run, "pai_threshold_combine flag", flag, int(any(c["want_rowflag"])))
+            ck.rows(run, "pai_threshold_combine d_rowflag", rf, c["want_rowflag"])
+            ck.that(fl == int(any(c["want_rowflag"])), run, "pai_threshold_combine flag", fl, int(any(c["want_rowflag"])))
             ck.rows(run, "pai_threshold_combine d_m", got, c["want"], skip={i for i, f in enumerate(c["want_rowflag"]) if f})
             fused = digit and not run["disable"]
             ck.that(has(names, "k_tfinish") and has(names, "k_tcomb_padic") == fused, run, "kernels of pai_threshold_combine", names)
             seen.append(got)
-            if c["poison"] is not None:
-                j, i, v = c["poison"]
-                bad = list(c["parts"][j])
-                bad[i] = v
-                _, flag, _ = combine(parts[:j] + [dev(nk, bad)] + parts[j + 1:])
-                ck.that(flag & 2 == 2, run, "pai_threshold_combine flag bit 1 (a part of the negative side that is no unit)", flag, 2)
+            if poisoned is not None:
+                _, fl, _ = combine(poisoned)
+                ck.that(fl & 2 == 2, run, "pai_threshold_combine flag bit 1 (a part of the negative side that is no unit)", fl, 2)
     ck.rows(c["runs"][1], "pai_threshold_combine: the two routes differ", seen[1], seen[0])
 
 
@@ -324,10 +362,12 @@ RUNNERS = {"segprod": run_segprod, "scan": run_scan, "smexp": run_smexp, "pack":
            "tpart": run_tpart, "tcomb": run_tcomb}
 
 
-def run_round(family, cls, seed, rnd, with_knobs, cov):
-    """one round of one family on the key of its class for that round; returns the number of comparisons made"""
-    h = handle(fz.key_bits_for(cls, rnd))
+def run_round(family, cls, seed, rnd, with_knobs, cov, stream=None, bits=None):
+    """one round of one family on the key of its class for that round (or on the key of `bits` bits); `stream`: None, or the
+    tests/_streams.Late placement the value operands arrive through (no kernel timers then: they synchronise, so the kernel-name
+    comparisons are left to the null-stream run).  Returns the number of comparisons made"""
+    h = handle(bits or fz.key_bits_for(cls, rnd))
     c = fz.case(family, h.key, seed, rnd)
-    ck = Checker(c, seed, cov)
-    RUNNERS[family](h, c, ck, with_knobs)
+    ck = Checker(c, seed, cov, profiled=stream is None)
+    RUNNERS[family](h, c, ck, with_knobs, stream)
     return ck.checks
