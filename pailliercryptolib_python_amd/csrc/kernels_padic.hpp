@@ -128,11 +128,22 @@ constexpr int PADIC_SQR_SYM_MAX_NL = 56;
 //                   tile (the entry and the exit write A and B), so base^2 is fetched once for the whole table build, and all
 //                   staged loads have landed before the exit stores into A and B.  Same digits, same LDS size, same table.
 //                   The compiler does not order an LDS read behind a direct-to-LDS load in flight: the waits are explicit.
-//                   (PAI_KMRBT_PARTS & 2, not shipped: the second pass of a product in the one-sum form with Karatsuba quotient
-//                   products on top, PADIC_KMRBT_RED.)
+//                   On top, each behind a compile-time switch so that it can be built and timed alone (profiles/r25/README.md):
+//                   the second pass of a product in the one-sum form with Karatsuba quotient products (PADIC_KMRBT_RED), the
+//                   first pass of a squaring with its off-diagonal products on the doubled operand (KRED_DSYM), and a
+//                   scheduling fence every few columns of a product's two passes, which keeps the compiler from hoisting the
+//                   LDS reads of d into the first pass and parking what they displace in AGPRs.
 #ifndef PAI_KMRBT_PARTS
-#define PAI_KMRBT_PARTS 1             // bit 0: the staged operand (shipped), bit 1: the second pass of a product in the one-sum form
-                                      // (measured alone and on top of the staged operand, not shipped: profiles/r20/README.md)
+#define PAI_KMRBT_PARTS 7             // bit 0: the staged operand, bit 1: the second pass of a product in the one-sum form (alone
+                                      // it did not pay on top of bit 0: profiles/r20/README.md; with the fence it does), bit 2: the
+                                      // first pass of a squaring sums its off-diagonal products on the doubled operand
+                                      // (mont_padic.hpp: KRED_DSYM).  The build before profiles/r25/: 1 with both fences at 0
+#endif
+#ifndef PAI_KMRBT_MUL_SCHED_EVERY
+#define PAI_KMRBT_MUL_SCHED_EVERY 4   // PADIC_LDS_KMRBT: columns between scheduling fences in the two passes of a product (0: none)
+#endif
+#ifndef PAI_KMRBT_SQR_SCHED_EVERY
+#define PAI_KMRBT_SQR_SCHED_EVERY 0   // ... and in the two passes of a squaring (measured, no gain: profiles/r25/README.md)
 #endif
 #ifndef PAI_KMRBT_REREAD
 #define PAI_KMRBT_REREAD 0            // 1: the product reads c from LDS again for its second pass (profiles/r20/README.md)
@@ -201,7 +212,10 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
         padic_to_digit_form<E>(A, B, M, row, P.ct_words, kdig, P.nd, nm, pm1, n0inv);
         if constexpr (MODE == PADIC_LDS_KMRB || MODE == PADIC_LDS_KMRBS || MODE == PADIC_LDS_KMRBT) {
             constexpr bool STAGE = MODE == PADIC_LDS_KMRBT && (PAI_KMRBT_PARTS & 1) != 0;
-            constexpr int BRED = MODE == PADIC_LDS_KMRBT ? ((PAI_KMRBT_PARTS & 2) ? E::PADIC_KMRBT_RED : E::PADIC_KMRBS_RED)
+            constexpr int SQF = MODE == PADIC_LDS_KMRBT ? PAI_KMRBT_SQR_SCHED_EVERY : 0;
+            constexpr int MULF = MODE == PADIC_LDS_KMRBT ? PAI_KMRBT_MUL_SCHED_EVERY : 0;
+            constexpr int BRED = MODE == PADIC_LDS_KMRBT ? (((PAI_KMRBT_PARTS & 2) ? E::PADIC_KMRBT_RED : E::PADIC_KMRBS_RED) |
+                                                            ((PAI_KMRBT_PARTS & 4) ? E::KRED_DSYM : 0))
                                  : MODE == PADIC_LDS_KMRBS ? E::PADIC_KMRBS_RED : E::PADIC_KMRB_RED;
             // STAGE: the table entry this wave's A and B hold as a product's right operand (wave-uniform), none at the top of a
             // tile: padic_to_digit_form above has just written both buffers
@@ -253,13 +267,13 @@ k_dec_a_padic(DecPadicParams P, const uint32_t* __restrict__ ct, uint32_t* __res
                     }
                 }
 #pragma unroll 1
-                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<BRED>(a, b, nb, n0inv);
+                for (int s = 0; s < nsq; ++s) E::template sqr_kara_reg_bal<BRED, SQF>(a, b, nb, n0inv);
                 if (idx != 0xFF) {
                     if constexpr (STAGE) {
                         // (in every product: waiting only in the steps that staged loses the gain in this build,
                         // profiles/r20/README.md)
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        E::template mul_kara_lds_bal<BRED, PAI_KMRBT_REREAD != 0>(a, b, A, B, nb, n0inv);
+                        E::template mul_kara_lds_bal<BRED, PAI_KMRBT_REREAD != 0, MULF>(a, b, A, B, nb, n0inv);
                     } else {
                         E::template mul_kara_reg_bal<BRED>(a, b, [&](int g, int c) -> uint4 { return tbl(idx, g, c); }, nb, n0inv);
                     }

@@ -1004,9 +1004,12 @@ struct Padic {
     // The Karatsuba identities of kara_pass (X_k, KRED: Y_k = U_k + U_(k-H) - E_(k-H), VF: X_k = V_k + V_(k-H) - D_(k-H)) are
     // identities over the integers and hold for signed limbs unchanged.  VF here serves all four FORMs: the sum of two
     // products is one chain V_k as well.  Cells: tools/kara_model.py (kara_pass_bal).
+#ifndef PAI_KMRBT_LAZY_DIFFS
+#define PAI_KMRBT_LAZY_DIFFS 1        // a fenced pass forms its half differences at the first column that takes them (0: at its head)
+#endif
     PAI_DEV static int32_t sfield(uint32_t v) { return (int32_t)(v << (32 - RB)) >> (32 - RB); }
     PAI_DEV static uint64_t smul(int32_t a, int32_t b) { return (uint64_t)((int64_t)a * (int64_t)b); }
-    template <int FORM, bool KRED = false, bool VF = false, int ONES = 0>
+    template <int FORM, bool KRED = false, bool VF = false, int ONES = 0, bool DSYM = false, int FENCE = 0>
     PAI_DEV static void kara_pass_bal(int32_t (&out)[NL], int32_t (&mq)[NL], const int32_t (&x)[NL], const int32_t (&y)[NL],
                                       const int32_t (&x2)[NL], const int32_t (&y2)[NL], const int32_t (&min)[NL],
                                       const int32_t* __restrict__ nm, uint32_t n0inv) {
@@ -1016,13 +1019,19 @@ struct Padic {
         constexpr int H = NL / 2, NP = 2 * H - 1;
         int32_t nx[H], dy[H], nx2[H], dy2[H];             // as in kara_pass; SYM without VF: dy2 = dy doubled
         int32_t yd[NL];
+        // with fences the differences are formed at the first column that takes them (k == H): a fence keeps them from
+        // sinking there by themselves, and until then they would only hold registers
+        constexpr bool LAZY = FENCE > 0 && PAI_KMRBT_LAZY_DIFFS;
+        auto diffs = [&]() {
 #pragma unroll
-        for (int i = 0; i < H; ++i) {
-            nx[i] = x[i + H] - x[i];
-            dy[i] = y[i] - y[i + H];
-            nx2[i] = SUM ? x2[i + H] - x2[i] : 0;
-            dy2[i] = SUM ? y2[i] - y2[i + H] : dy[i] * 2;
-        }
+            for (int i = 0; i < H; ++i) {
+                nx[i] = x[i + H] - x[i];
+                dy[i] = y[i] - y[i + H];
+                nx2[i] = SUM ? x2[i + H] - x2[i] : 0;
+                dy2[i] = SUM ? y2[i] - y2[i + H] : dy[i] * 2;
+            }
+        };
+        if (!LAZY) diffs();
 #pragma unroll
         for (int i = 0; i < NL; ++i) yd[i] = y[i] * 2;
         auto half = [&](int o, int j) -> uint64_t {
@@ -1065,6 +1074,11 @@ struct Padic {
             // pairs' signed products, the latter on e, the chain that does not wait for the carry.  The parts of S_k double
             // their bounds (|V_k| <= 2 H 2^56) and wrap as before; the finished column is the one of the two-sum form, below
             // 2^62.76.  Cells: tools/kara_model.py (kara_pass_bal_sum).
+            // DSYM (the first pass of a squaring; KRED_DSYM): the off-diagonal products x_i x_l, i < l, take the doubled operand
+            // (yd, dy2) as the doubled pass does and go straight onto s and e: no chain of their own (off, nd), no 64-bit shift
+            // and no joining addition for it.  |2 x_l| <= 2^29 and |2 (x_l - x_(l+H))| <= 2^30 are int32, a product is at most
+            // 2^59, and x_i (2 x_l) == (x_i x_l) << 1 modulo 2^64, which is all a stored sum needs: S_k, e and with them d_k, mq,
+            // out and every carry are bit for bit those of the shifted form.  Cells: tools/kara_model.py (ones, dsym).
             constexpr int NU = H + NP;                    // S_0 .. S_(NU-1)
             uint64_t ss[NU];
 #pragma unroll
@@ -1072,6 +1086,7 @@ struct Padic {
                 const bool mid = k >= H && k - H < NP;
                 const int j = k - H;
                 uint64_t s = 0, off = 0;
+                if (LAZY && k == H) diffs();
                 if (k < NP) {
                     const int lo = k < H ? 0 : k - H + 1, hi = k < H ? k : H - 1;
 #pragma unroll
@@ -1079,6 +1094,7 @@ struct Padic {
                         const int l = k - i;
                         if (DBL) s += smul(x[i], yd[l]);
                         else if (!SYM) s += smul(x[i], y[l]);
+                        else if (i < l && DSYM) s += smul(x[i], yd[l]);
                         else if (i < l) off += smul(x[i], y[l]);
                         else if (i == l) s += smul(x[i], y[i]);
                         if (SUM) s += smul(x2[i], y2[l]);
@@ -1091,12 +1107,13 @@ struct Padic {
                         const int l = j - i;
                         if (DBL) s += smul(x[H + i], yd[H + l]);
                         else if (!SYM) s += smul(x[H + i], y[H + l]);
+                        else if (i < l && DSYM) s += smul(x[H + i], yd[H + l]);
                         else if (i < l) off += smul(x[H + i], y[H + l]);
                         else if (i == l) s += smul(x[H + i], y[H + i]);
                         if (SUM) s += smul(x2[H + i], y2[H + l]);
                     }
                 }
-                if (SYM) s += off << 1;
+                if (SYM && !DSYM) s += off << 1;
                 // quotient terms of the digits known before the previous column
                 if (k < NP) {
                     const int lo0 = k < H ? 0 : k - H + 1, hi0 = k < H ? k - 1 : H - 1;
@@ -1124,11 +1141,12 @@ struct Padic {
                         const int l = j - i;
                         if (DBL) e += smul(nx[i], dy2[l]);
                         else if (!SYM) e += smul(nx[i], dy[l]);
+                        else if (i < l && DSYM) e += smul(nx[i], dy2[l]);
                         else if (i < l) nd += smul(nx[i], dy[l]);
                         else if (i == l) e += smul(nx[i], dy[i]);
                         if (SUM) e += smul(nx2[i], dy2[l]);
                     }
-                    if (SYM) e += nd << 1;
+                    if (SYM && !DSYM) e += nd << 1;
 #pragma unroll
                     for (int i = lo; i <= hi; ++i) {
                         if (i == j && k < NL) e += smul(mq[i], ndp[0]);
@@ -1156,6 +1174,7 @@ struct Padic {
                 }
                 if (k < NU) ss[k] = s;
                 carry = (uint64_t)((int64_t)(k < NL ? d : d + (1ull << (RB - 1))) >> RB);
+                if (FENCE > 0 && k % FENCE == FENCE - 1) __builtin_amdgcn_sched_barrier(0);
             }
             out[NL - 1] = (int32_t)carry;
             return;
@@ -1163,6 +1182,7 @@ struct Padic {
 #pragma unroll
         for (int k = 0; k < 2 * NL - 1; ++k) {
             uint64_t t = 0;                               // the product column X_k, exact modulo 2^64
+            if (LAZY && k == H) diffs();
             if constexpr (VF) {
                 const bool mid = k >= H && k - H < NP;
                 uint64_t vk = 0, off = 0, nd = 0;
@@ -1288,6 +1308,7 @@ struct Padic {
                 }
             }
             carry = (uint64_t)((int64_t)(k < NL ? d : d + (1ull << (RB - 1))) >> RB);
+            if (FENCE > 0 && k % FENCE == FENCE - 1) __builtin_amdgcn_sched_barrier(0);
         }
         out[NL - 1] = (int32_t)carry;
     }
@@ -1298,21 +1319,27 @@ struct Padic {
     static constexpr int PADIC_KMRB_RED = PADIC_KMR_RED | KRED_VFS;
     // KRED_ONES = the passes that have both KRED and VF (both of a squaring, the first of a product) keep ONE stored sum per
     // column, S_k = [2] V_k + U_k (kara_pass_bal: ONES); KRED_ONES2 on top = the terms of the newest quotient digit are added
-    // to the sum and to the column separately.  Kernel mode PADIC_LDS_KMRBS.  The second pass of a product keeps its form in the
-    // shipped kernels: in the one-sum form with Karatsuba quotient products (PADIC_KMRBT_RED below) it is shorter and gains by
-    // itself, but nothing on top of the staged right operand (profiles/r20/README.md).
+    // to the sum and to the column separately.  Kernel mode PADIC_LDS_KMRBS.  The second pass of a product keeps its form in
+    // this mode; in the one-sum form with Karatsuba quotient products (PADIC_KMRBT_RED below) it is shorter, gained nothing by
+    // itself on top of the staged right operand (profiles/r20/README.md) and runs in mode PADIC_LDS_KMRBT since the product's
+    // columns are fenced (profiles/r25/README.md).
     static constexpr int KRED_ONES = 128, KRED_ONES2 = 256;
 #ifndef PAI_KMRBS_NEWEST_TWICE
 #define PAI_KMRBS_NEWEST_TWICE 0      // 1: build the other placement of the newest digit's terms (profiles/r17/README.md)
 #endif
     static constexpr int PADIC_KMRBS_RED = PADIC_KMRB_RED | KRED_ONES | (PAI_KMRBS_NEWEST_TWICE ? KRED_ONES2 : 0);
     static constexpr int ones(int RED) { return (RED & KRED_ONES) ? ((RED & KRED_ONES2) ? 2 : 1) : 0; }
-    template <int RED = 0>
+    // KRED_DSYM = the first pass of a squaring in the one-sum form sums its off-diagonal products on the doubled operand
+    // (kara_pass_bal: DSYM).  Kernel mode PADIC_LDS_KMRBT with PAI_KMRBT_PARTS & 4 (profiles/r25/README.md).
+    static constexpr int KRED_DSYM = 512;
+    // SQF / MULF: a scheduling fence (sched_barrier) after every SQF resp. MULF columns of either pass (0: none), as
+    // kara2_step_bal has: the scheduler works on a few columns at a time instead of a whole pass (profiles/r25/README.md)
+    template <int RED = 0, int SQF = 0>
     PAI_DEV static void sqr_kara_reg_bal(int32_t (&a)[NL], int32_t (&b)[NL], const int32_t* __restrict__ nm, uint32_t n0inv) {
         constexpr bool VF = (RED & KRED_VF) != 0;
         int32_t m[NL], w[NL], m2[NL], v[NL];
-        kara_pass_bal<KARA_SQR, kred(RED, KARA_SQR), VF, ones(RED)>(w, m, a, a, a, a, m, nm, n0inv);
-        kara_pass_bal<KARA_SQR2, kred(RED, KARA_SQR2), VF, ones(RED)>(v, m2, a, b, a, b, m, nm, n0inv);
+        kara_pass_bal<KARA_SQR, kred(RED, KARA_SQR), VF, ones(RED), (RED & KRED_DSYM) != 0, SQF>(w, m, a, a, a, a, m, nm, n0inv);
+        kara_pass_bal<KARA_SQR2, kred(RED, KARA_SQR2), VF, ones(RED), false, SQF>(v, m2, a, b, a, b, m, nm, n0inv);
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }
     }
@@ -1348,21 +1375,21 @@ struct Padic {
             r[4 * ch] = (int32_t)t.x; r[4 * ch + 1] = (int32_t)t.y; r[4 * ch + 2] = (int32_t)t.z; r[4 * ch + 3] = (int32_t)t.w;
         }
     }
-    template <int RED, bool REREAD>
+    template <int RED, bool REREAD, int MULF = 0>
     PAI_DEV static void mul_kara_lds_bal(int32_t (&a)[NL], int32_t (&b)[NL], const uint4* C, const uint4* D,
                                          const int32_t* __restrict__ nm, uint32_t n0inv) {
         constexpr int ONES2ND = kred(RED, KARA_MUL2) ? ones(RED) : 0;
         int32_t c[NL], d[NL], m[NL], w[NL], m2[NL], v[NL];
         load_digit_bal(C, c);
-        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0, ones(RED)>(w, m, a, c, a, c, m, nm, n0inv);
+        kara_pass_bal<KARA_MUL, kred(RED, KARA_MUL), (RED & KRED_VFM) != 0, ones(RED), false, MULF>(w, m, a, c, a, c, m, nm, n0inv);
         load_digit_bal(D, d);
         if constexpr (REREAD) {
             int32_t c2[NL];
             asm volatile("" ::: "memory");
             load_digit_bal(C, c2);
-            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND>(v, m2, a, d, b, c2, m, nm, n0inv);
+            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND, false, MULF>(v, m2, a, d, b, c2, m, nm, n0inv);
         } else {
-            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND>(v, m2, a, d, b, c, m, nm, n0inv);
+            kara_pass_bal<KARA_MUL2, kred(RED, KARA_MUL2), (RED & KRED_VFS) != 0, ONES2ND, false, MULF>(v, m2, a, d, b, c, m, nm, n0inv);
         }
 #pragma unroll
         for (int j = 0; j < NL; ++j) { a[j] = w[j]; b[j] = v[j]; }

@@ -1,7 +1,8 @@
 // The 36-limb digit-pair decrypt kernel in mode PADIC_LDS_KMRBT (kernels_padic.hpp: PADIC_LDS_KMRBS with the right operand of a
 // product staged in LDS ahead of the step's squarings), the default for primes of 677..1024 bits.  Own translation unit, as
 // padic_dec_kmrbs_kernels.hip, which keeps the kernel that loads the operand into registers at the head of the product
-// (PAI_DISABLE=padic_stage).  -DPAI_KMRBT_PARTS / -DPAI_KMRBT_REREAD build the measured variants (profiles/r20/README.md).
+// (PAI_DISABLE=padic_stage).  -DPAI_KMRBT_PARTS / -DPAI_KMRBT_REREAD / -DPAI_KMRBT_MUL_SCHED_EVERY / -DPAI_KMRBT_SQR_SCHED_EVERY /
+// -DPAI_KMRBT_LAZY_DIFFS build the measured variants (profiles/r20/README.md, profiles/r25/README.md).
 #include "geo_ops.hpp"
 #include "kernels_padic.hpp"
 #include "launch.hpp"

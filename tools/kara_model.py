@@ -365,6 +365,8 @@ HB = B >> 1                           # 2^28
 # quotient digit go onto the sum and onto the column separately instead of onto the sum before the column is formed.
 ONES, ONES2 = 128, 256
 KMRBS_RED = KMRB_RED | ONES           # Padic::PADIC_KMRBS_RED: what kernel mode PADIC_LDS_KMRBS runs
+DSYM = 512                            # Padic::KRED_DSYM: the first pass of a squaring sums its off-diagonal products on the doubled
+                                      # operand (kernel mode PADIC_LDS_KMRBT with PAI_KMRBT_PARTS & 4)
 M64 = (1 << 64) - 1
 
 
@@ -418,13 +420,17 @@ def from_balanced_plus_p(x, nb, less):
 class BalStats:
     def __init__(self):
         self.max_d = self.max_v = self.max_u = self.max_e = 0
+        self.max_s = 0                        # largest |S_k| of a one-sum pass as a plain integer (the cell holds it modulo 2^64)
         self.max_c = 0                        # largest |carry| out of a finished column
         self.at_d = None                      # (form, column) of the largest finished column
         self.red_macs = 0
 
 
-def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False, ones=0):
-    """One pass of kara_pass_bal<FORM, KRED, VF, ONES> on signed limb lists; returns (out limbs, quotient limbs)."""
+def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False, vf=False, ones=0, dsym=False, trace=None):
+    """One pass of kara_pass_bal<FORM, KRED, VF, ONES, DSYM> on signed limb lists; returns (out limbs, quotient limbs).
+    dsym (one-sum first pass of a squaring only): the off-diagonal products take the doubled operand (yd, dy2) and go straight
+    onto s and e, in 64-bit cells that wrap, instead of a chain of their own that is shifted.  trace: a list that receives the
+    carry out of every column."""
     form = int(form)
     sym, dbl, summ = form == SQR, form == SQR2, form == MUL2
     second = dbl or summ
@@ -518,11 +524,13 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
                         s = (s + smul(x[o + i], yd[o + l])) & M64
                     elif not sym:
                         s = (s + smul(x[o + i], y[o + l])) & M64
+                    elif i < l and dsym:
+                        s = (s + smul(x[o + i], yd[o + l])) & M64
                     elif i < l:
                         off = (off + smul(x[o + i], y[o + l])) & M64
                     elif i == l:
                         s = (s + smul(x[o + i], y[o + i])) & M64
-            if sym:
+            if sym and not dsym:
                 s = (s + (off << 1)) & M64
             if k < NP:
                 lo0, hi0 = (0, k - 1) if k < H else (k - H + 1, H - 1)
@@ -551,11 +559,13 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
                         e = (e + smul(nx[i], dy2[l])) & M64
                     elif not sym:
                         e = (e + smul(nx[i], dy[l])) & M64
+                    elif i < l and dsym:
+                        e = (e + smul(nx[i], dy2[l])) & M64
                     elif i < l:
                         nd = (nd + smul(nx[i], dy[l])) & M64
                     elif i == l:
                         e = (e + smul(nx[i], dy[i])) & M64
-                if sym:
+                if sym and not dsym:
                     e = (e + (nd << 1)) & M64
                 for i in range(lo, hi + 1):
                     if i == j and k < NL:
@@ -587,11 +597,21 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
                     assert i32(dm[k - H])
             else:
                 out[k - NL] = sfield(d)
+            # S_k on plain integers: [2] V_k + U_k with every quotient digit up to mq[k]; the cell is that modulo 2^64
+            s_int = 0
+            for o, jj, on in ((0, k, k < NP), (H, j, mid)):
+                if on:
+                    lo, hi = rng(jj)
+                    s_int += (2 if dbl else 1) * dot(x[o:o + H], y[o:o + H], lo, hi, jj) + dot(mq[o:o + H], nm[o:o + H], lo, hi, jj)
+            assert s_int & M64 == s, (k, s_int, s)
+            st.max_s = max(st.max_s, abs(s_int))
             if k < H + NP:
                 ss[k] = s
             else:
                 assert s == 0
             carry = finish(k, d - (1 << 64) if d >> 63 else d, school)
+            if trace is not None:
+                trace.append(carry)
             continue
         t = 0
         if vf:
@@ -740,6 +760,8 @@ def kara_pass_bal(form, x, y, mnin, nm, n0inv, st, x2=None, y2=None, kred=False,
             else:
                 assert u == 0
         carry = finish(k, d, school)
+        if trace is not None:
+            trace.append(carry)
     assert i32(carry)
     out[NL - 1] = carry
     st.red_macs = macs
@@ -774,7 +796,8 @@ def sqr_kara_bal(al, bl, p, st, red=KMRB_RED):
     NL = len(al)
     R = 1 << (RB * NL)
     nm, n0inv = _bal_ctx(p, NL)
-    w, m = kara_pass_bal(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF), ones=red_ones(red))
+    w, m = kara_pass_bal(SQR, al, al, [0] * NL, nm, n0inv, st, kred=bool(red >> SQR & 1), vf=bool(red & VF), ones=red_ones(red),
+                         dsym=bool(red & DSYM))
     v, m2 = kara_pass_bal(SQR2, al, bl, m, nm, n0inv, st, kred=bool(red >> SQR2 & 1), vf=bool(red & VF), ones=red_ones(red))
     a, b = value(al), value(bl)
     W, M, V, M2 = value(w), value(m), value(v), value(m2)
@@ -786,7 +809,7 @@ def sqr_kara_bal(al, bl, p, st, red=KMRB_RED):
 
 
 # ---- the second pass of a product in the one-sum form (kara_pass_bal<KARA_MUL2, true, true, ONES>; kernel mode PADIC_LDS_KMRBT
-# built with -DPAI_KMRBT_PARTS=3, not the shipped build) ----
+# with PAI_KMRBT_PARTS & 2: the default since profiles/r25/) ----
 # v = (x y + x2 y2 - min + m' p) / R with Karatsuba quotient products and ONE stored sum per column: S_k = V_k + U_k, where V_k now
 # sums the half products of BOTH pairs (|V_k| <= 2 H 2^56) and -D_(k-H) of both pairs goes onto e, the chain that does not wait for
 # the previous column's carry.  Every cell is a 64-bit word that WRAPS; the finished column, read as a signed 64-bit integer, must
